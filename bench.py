@@ -6,10 +6,17 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-One process per GPU; weak scaling (B per GPU fixed).  Rank 0 prints ONE JSON line with the metric, the
-roofline of the dominant kernel (timed live with hipEvents on the launch stream inside the timed region)
-and, at N=1, the CPU baseline (the oracle restatement, oracle/cunet_ref.py, timed on the host cores on a
-bounded sample: B=4 256x256 fp32 fwd+bwd, 4 iterations).
+One process per GPU; weak scaling (B per GPU fixed).  Rank 0 prints ONE JSON line with the metric.  A plain run
+sets up, warms up, times the --steps steps and prints that line, nothing else.  --full adds the roofline of the
+dominant kernel (timed live with hipEvents on the launch stream inside the timed region) and, at N=1, the CPU
+baseline (the oracle restatement, oracle/cunet_ref.py, timed on the host cores on a bounded sample: B=4 256x256
+fp32 fwd+bwd, 4 iterations); --no-roofline / --no-cpu-baseline drop either from a --full run.
+A --full run brackets every conv launch of the timed region with a hipEvent pair (about 0.18 ms per step,
+profiles/r03_roofline_overhead.txt), so a plain run's ms_per_step is that much lower than a --full run's and than the
+default runs recorded before --full existed (BENCH_r0*.json): less instrumentation, not faster kernels.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs()): the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -31,18 +38,23 @@ PEAK_BF16_TFLOPS = 2500.0      # dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_F32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
 PMC_FILE = "r04_pmc.json"      # scratch/pmc_collect.py output for the current kernels (see roofline.traffic)
+DUMP_BYTES = 60 * 10**6        # --dump-outputs: at most this many bytes of .npy data in all (under 64 MB)
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline of the dominant kernel (extra instrumented steps) and, on one GPU, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, <= 60 MB in all)")
     ap.add_argument("--fwd-only", action="store_true", help="inference forward (eval mode) instead of the training step")
     ap.add_argument("--graph", action="store_true", help="with --fwd-only: replay a hipGraph-captured forward (configs[4])")
     ap.add_argument("--dropout-active", action="store_true",
@@ -60,7 +72,10 @@ def parse():
     ap.add_argument("--workload", default="unet", choices=["unet", "gan-cls", "gan-est"],
                     help="unet: cUNet fwd+bwd (the headline metric); gan-cls / gan-est: one full GAN iteration "
                          "(D update + G update) of t_cls_train.py / t_est_train.py (configs[2] / configs[3])")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
 
 
 def self_launch(n):
@@ -98,6 +113,28 @@ def cpu_baseline(size, iters=3, batch=4):
     return {"value": round(batch / med, 4), "unit": "images/sec", "cores": threads, "kind": "port",
             "sample": f"oracle fwd+bwd (eval-mode dropout), B={batch} {size}x{size} fp32, median of {iters} after 1 warm-up "
                       f"({med:.2f} s/iter), os.cpu_count()={os.cpu_count()}"}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each (name, tensor) as out_dir/<name>.npy, float64 tensors as float64 and everything else as
+    float32.  If the arrays together exceed DUMP_BYTES, each is cut to the same fraction of its elements by a fixed sample:
+    the flat elements at np.random.default_rng(0).choice(numel, k, replace=False), sorted -- the same indices for the same
+    shapes on every run and every build.  Returns {name: [shape written, shape computed]}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = [(n, t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()) for n, t in arrays]
+    total = sum(v.nbytes for _, v in host)
+    scale = min(1.0, (DUMP_BYTES - 4096 * len(host)) / max(total, 1))      # headroom for the .npy headers
+    index = {}
+    for name, v in host:
+        full_shape = list(v.shape)
+        k = max(1, int(v.size * scale))
+        if k < v.size:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, k, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        index[name] = [list(v.shape), full_shape]
+    return index
 
 
 def main():
@@ -195,7 +232,24 @@ def main():
         if reducer is not None:
             reducer.finalize()
         opt.step()
-        return loss
+        return loss, out
+
+    def outputs(last):
+        """What a caller of the timed step receives, for --dump-outputs: the returned values, and for training steps the
+        parameters the optimizer left and the (all-reduced) gradients it stepped with, each network's flattened in parameter order."""
+        def flat(ts):
+            return torch.cat([t.detach().reshape(-1).float() for t in ts])
+        if gan is not None:
+            arrays = [("losses", torch.cat([v.detach().float().reshape(-1) for v in last]))]
+            for tag, m in (("generator", gan.inference), ("discriminator", gan.discriminator)):
+                ps = [p for p in m.parameters() if p.grad is not None]
+                arrays += [(tag + "_params", flat(m.parameters())), (tag + "_grads", flat(p.grad for p in ps))]
+            return arrays
+        if a.fwd_only:
+            return [("output", last)]
+        loss, out = last
+        return [("loss", loss.reshape(1)), ("output", out), ("params", flat(net.parameters())),
+                ("grads", flat(p.grad for p in net.parameters() if p.grad is not None))]
 
     def barrier():
         torch.cuda.synchronize()
@@ -210,10 +264,11 @@ def main():
     families = [_lib.FAM_CONV_FWD, _lib.FAM_WGRAD, _lib.FAM_CONV_DGRAD]
     if gan is not None:       # discriminator stride-2 convs and the estimator's pointwise convs
         families += [_lib.FAM_CONV_S2, _lib.FAM_WGRAD_S2, _lib.FAM_CONV1X1]
-    do_roof = (not a.no_roofline) and rank == 0
+    roofline = a.full and not a.no_roofline
+    do_roof = roofline and rank == 0
     pre_stats = None
     families_timed = families
-    if not a.no_roofline and gan is not None:
+    if roofline and gan is not None:
         # GAN workloads launch ~550 instrumented kernels per iteration and the hipEvent pair around each costs ~5 us of stream time
         # (3.5 ms of a 31 ms iteration).  One extra, untimed, fully instrumented iteration finds the dominant family and gives the
         # other families' figures; the timed region then brackets the dominant family only (every one of its launches).  Every rank
@@ -247,6 +302,9 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = None
+    if a.dump_outputs and rank == 0:             # before the roofline's extra steps below can change any of it
+        dumped = dump_outputs(a.dump_outputs, outputs(last))
 
     roof = None
     measured_flops = None
@@ -386,7 +444,9 @@ def main():
             res["roofline"] = roof
         if _lib.LOADED_PATH and os.path.realpath(_lib.LOADED_PATH) != os.path.realpath(_lib.LIB_PATH):
             res["library"] = _lib.LOADED_PATH              # WU_AB_LIB: an A/B run on another build, never a headline number
-        if world == 1 and not a.no_cpu_baseline and not a.fwd_only and gan is None:
+        if dumped is not None:
+            res["outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+        if a.full and world == 1 and not a.no_cpu_baseline and not a.fwd_only and gan is None:
             res["cpu_baseline"] = cpu_baseline(a.size)
         print(json.dumps(res), flush=True)
     if use_ddp:

@@ -65,7 +65,10 @@ def test_cunet_train_mode_masks(golden_dir):
 
 
 @pytest.mark.parametrize("tag", ["b2_64", "b3_128"])
-def test_sndisc(golden_dir, tag):
+def test_sndisc(golden_dir, tag, monkeypatch):
+    # PyTorch's own CPU convolution, not oneDNN's: oneDNN picks its conv algorithm by the host's ISA, and on AVX2-only
+    # dispatch its fp32 weight gradient of conv1.0 lands 7e-4 from the float64 value (the golden is within 1e-6 of it)
+    monkeypatch.setattr(torch.backends.mkldnn, "enabled", False)
     g = _load(golden_dir, f"sndisc_{tag}.npz")
     batch, size, soft, seed, nc = [int(v) for v in g["meta"]]
     p = O.make_sndisc_params(nc, seed)
