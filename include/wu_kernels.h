@@ -362,6 +362,44 @@ int wu_maxpool3s2_fwd(const void* x, int ldx, void* y, int ldy, uint8_t* argmax,
 int wu_maxpool3s2_bwd(const void* dy, int lddy, const uint8_t* argmax, const void* x, int ldx, void* dx, int lddx,
                       int N, int H, int W, int C, int gate_act, int dtype, void* stream);
 
+/* ---- trainable ResNet-101 (classifier.py:106 / estimator.py:143 trained from scratch, sh/train_classifier.sh, sh/train_estimator.sh) --------
+ * Train-mode BatchNorm and the weight gradients the frozen estimator does not need.  Rows = the M = N*H*W pixels of an NHWC tensor (pixel
+ * stride ld, 16-byte aligned); C % 64 == 0.  Per-channel vectors are fp32; `stats` is float[2][C] = {mean[C], rstd[C]},
+ * rstd = 1 / sqrt(var_biased + eps).  Every reduction writes per-split partial sums into the caller-owned `workspace` (size from the
+ * matching *_workspace query) and folds them in split order: deterministic, no atomics.
+ *
+ * Batch statistics of x (shifted one-pass sums, robust on offset data); running_mean / running_var (may be NULL) are updated as
+ * nn.BatchNorm2d does in training: r = momentum * batch + (1 - momentum) * r, running_var from the UNBIASED variance (n / (n - 1));
+ * num_batches_tracked (int64, may be NULL) += 1. */
+size_t wu_bn_stats_workspace(long long M, int C, int dtype);
+int wu_bn_stats(const void* x, int ldx, long long M, int C, float eps, float momentum, float* stats,
+                float* running_mean, float* running_var, long long* num_batches_tracked,
+                void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* y = act(x * scale + shift [+ x2 * scale2 + shift2 | + residual]),  scale = gamma * rstd, shift = beta - mean * scale (per branch):
+ * a BatchNorm + ReLU, a Bottleneck's relu(bn3(conv3) + bn_ds(downsample)) (x2 != NULL) or relu(bn3(conv3) + identity) (residual != NULL). */
+int wu_bn_apply(const void* x, int ldx, const float* stats, const float* gamma, const float* beta,
+                const void* x2, int ldx2, const float* stats2, const float* gamma2, const float* beta2,
+                const void* residual, int ldres, void* y, int ldy, long long M, int C, int act, int dtype, void* stream);
+/* BatchNorm backward.  gg = g * act'(y) (y = the stored activation output, NULL: gg = g).  dbeta = sum gg, dgamma = sum gg * xhat (overwritten),
+ * dx = gamma * rstd * (gg - mean(gg) - xhat * mean(gg * xhat)).  Optional second branch sharing gg (x2 != NULL: dgamma2, dbeta2, dx2) and
+ * optional copy of gg itself (gres != NULL: the identity path of a Bottleneck). */
+size_t wu_bn_bwd_workspace(long long M, int C, int dtype);
+int wu_bn_bwd(const void* g, int ldg, const void* y, int ldy, int act,
+              const void* x, int ldx, const float* stats, const float* gamma, float* dgamma, float* dbeta, void* dx, int lddx,
+              const void* x2, int ldx2, const float* stats2, const float* gamma2, float* dgamma2, float* dbeta2, void* dx2, int lddx2,
+              void* gres, int ldgres, long long M, int C, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* Pointwise conv weight gradient: dw[Cout][Cin] (fp32) (+)= sum over the N x Hc x Wc rows r of dy[r][co] * x[pix(r)][ci], pix as in
+ * wu_conv1x1_fwd (in_stride 2: the downsample conv's gather, Hc = (Hin-1)/2+1).  Matrix cores (bf16, or exact fp32); split-K over rows.
+ * Cin % 64 == 0, Cout % 64 == 0; accumulate != 0 adds into dw. */
+size_t wu_conv1x1_wgrad_workspace(long long M, int Cin, int Cout);
+int wu_conv1x1_wgrad(const void* x, int ldx, const void* dy, int lddy, float* dw, void* workspace, size_t workspace_bytes,
+                     int N, int Hc, int Wc, int in_stride, int Hin, int Win, int Cin, int Cout, int accumulate, int dtype, void* stream);
+/* Stem weight gradient: dw_oihw[64][3][7][7] (fp32) (+)= the gradient of nn.Conv2d(3, 64, 7, stride=2, padding=3) from the fp32 NCHW
+ * image x (N,3,H,W; any H, W) and dy (N,Ho,Wo,64) in `dtype`, Ho = (H-1)/2 + 1. */
+size_t wu_stem7x7_wgrad_workspace(int N, int H, int W);
+int wu_stem7x7_wgrad(const float* x_nchw, const void* dy, int lddy, float* dw_oihw, void* workspace, size_t workspace_bytes,
+                     int N, int H, int W, int accumulate, int dtype, void* stream);
+
 /* ---- input pipeline (t_cls_train.py:81-108: the torchvision / PIL transforms every training image goes through) ----------
  * A batch of decoded RGB images lives in one uint8 buffer `src`; image n starts at byte geo[n].src_off, is src_h x src_w pixels
  * with a row stride of src_ld pixels.  `geo` is an array of N records of wu_image_geo_bytes() (= 72) bytes:

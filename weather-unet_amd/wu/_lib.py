@@ -90,6 +90,15 @@ SIGNATURES = {
     "wu_stem7x7_dgrad": (I, [P, I, P, P, I, I, I, I, I, P]),
     "wu_maxpool3s2_fwd": (I, [P, I, P, I, P, I, I, I, I, I, P]),
     "wu_maxpool3s2_bwd": (I, [P, I, P, P, I, P, I, I, I, I, I, I, I, P]),
+    "wu_bn_stats_workspace": (SZ, [ctypes.c_longlong, I, I]),
+    "wu_bn_stats": (I, [P, I, ctypes.c_longlong, I, F, F, P, P, P, P, P, SZ, I, P]),
+    "wu_bn_apply": (I, [P, I, P, P, P, P, I, P, P, P, P, I, P, I, ctypes.c_longlong, I, I, I, P]),
+    "wu_bn_bwd_workspace": (SZ, [ctypes.c_longlong, I, I]),
+    "wu_bn_bwd": (I, [P, I, P, I, I, P, I, P, P, P, P, P, I, P, I, P, P, P, P, P, I, P, I, ctypes.c_longlong, I, P, SZ, I, P]),
+    "wu_conv1x1_wgrad_workspace": (SZ, [ctypes.c_longlong, I, I]),
+    "wu_conv1x1_wgrad": (I, [P, I, P, I, P, P, SZ, I, I, I, I, I, I, I, I, I, I, P]),
+    "wu_stem7x7_wgrad_workspace": (SZ, [I, I, I]),
+    "wu_stem7x7_wgrad": (I, [P, P, I, P, P, SZ, I, I, I, I, I, P]),
     "wu_image_geo_bytes": (SZ, []),
     "wu_image_workspace_bytes": (SZ, [I, I, I]),
     "wu_image_geometry": (I, [P, P, P, SZ, P, P, I, I, I, I, P]),
