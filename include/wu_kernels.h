@@ -419,6 +419,43 @@ int wu_image_geometry(const uint8_t* src, const void* geo, void* workspace, size
  * with Pillow's arithmetic; then (dst_nchw != NULL) ToTensor + Normalize(0.5, 0.5) into (N,3,S,S) fp32. */
 int wu_image_color_jitter(uint8_t* img_u8, const float* factors, const int* order, float* dst_nchw, int N, int S, void* stream);
 
+/* ---- InceptionV3 forward for FID / Inception Score (eval/fid_score.py, eval/inception.py, eval/inception_score.py) ---------------------
+ * pytorch-fid's FID InceptionV3 and torchvision's Inception3 in eval mode: every BasicConv2d is conv (no bias) + BatchNorm(eps 1e-3) + ReLU,
+ * folded by the caller into one conv with an fp32 bias.  Forward only; no atomics, every result is deterministic.
+ *
+ * Generic KH x KW conv (every conv of the network, and the fc head as a 1x1 over N x 1 x 1 pixels) as an implicit GEMM on the matrix cores:
+ *     y = act(conv(x, w) + bias),  x (N,H,W,Cin) ld=ldx,  y (N,Ho,Wo,Cout) ld=ldy,  Ho = (H + 2 pad_h - KH) / stride_h + 1 (likewise Wo)
+ * Zero padding; act WU_ACT_NONE or WU_ACT_RELU; only channels [0, Cout) of y are written (a Mixed block's branches write their channel
+ * slices of the concat buffer).  Cin % 16 == 0, Cout % 16 == 0, KH, KW <= 15, pad < kernel, ldx / ldy multiples of 8, x / y / w_packed /
+ * bias (may be NULL) 16-byte aligned.  w_packed: wu_conv_kxk_packed_bytes() bytes written once per weight by wu_pack_conv_kxk from the
+ * OIHW fp32 weight [Cout][Cin_w][KH][KW]; input channels Cin_w..Cin-1 are zero (the first layer's 3 image channels padded to 16). */
+size_t wu_conv_kxk_packed_bytes(int Cout, int Cin, int KH, int KW, int dtype);
+int wu_pack_conv_kxk(const float* w_oihw, void* w_packed, int Cout, int Cin_w, int Cin, int KH, int KW, int dtype, void* stream);
+int wu_conv_kxk_fwd(const void* x, int ldx, const void* w_packed, const float* bias, void* y, int ldy,
+                    int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride_h, int stride_w, int pad_h, int pad_w,
+                    int act, int dtype, void* stream);
+/* 3x3 pools, x (N,H,W,C) -> y (N,Ho,Wo,C), Ho = (H + 2 pad - 3) / stride + 1; C % 4 == 0, 16-byte aligned x / y.
+ *   WU_POOL_MAX:          F.max_pool2d(x, 3, stride, pad) (stride 1 or 2, pad 0 or 1; padding never wins)
+ *   WU_POOL_AVG:          F.avg_pool2d(x, 3, 1, 1) (count_include_pad=True: torchvision's InceptionA / C / E)
+ *   WU_POOL_AVG_EXCL_PAD: F.avg_pool2d(x, 3, 1, 1, count_include_pad=False) (the FID InceptionV3) */
+#define WU_POOL_MAX 0
+#define WU_POOL_AVG 1
+#define WU_POOL_AVG_EXCL_PAD 2
+int wu_pool3x3_fwd(const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C, int stride, int pad, int mode, int dtype, void* stream);
+/* Global average pool: out[n * ldo + c] = mean over H x W of x[n,:,:,c] (fp32 out; fp64 sums in a fixed order).  C % 4 == 0. */
+int wu_global_avgpool_fwd(const void* x, int ldx, float* out, int ldo, int N, int H, int W, int C, int dtype, void* stream);
+/* Network input: src_u8 == 0: NCHW fp32 images (N,3,Hin,Win); src_u8 != 0: dense NHWC uint8 (N,Hin,Win,3), read as x / 255 (correctly
+ * rounded, as numpy's float32 division).  v = v * in_scale + in_shift (1, 0 = none; 0.5, 0.5 maps [-1, 1] generator output to [0, 1]),
+ * bilinear resize to Ho x Wo (F.interpolate, align_corners=False, no antialias; Ho x Wo = Hin x Win copies), normalize != 0: 2 v - 1.
+ * y (N,Ho,Wo,cpad) ld=ldy in `dtype`, channels 3..cpad-1 zero; cpad % 4 == 0, 4 <= cpad <= ldy. */
+int wu_inception_input(const void* src, int src_u8, int N, int Hin, int Win, float in_scale, float in_shift, int normalize,
+                       void* y, int ldy, int Ho, int Wo, int cpad, int dtype, void* stream);
+/* Feature statistics for the FID: for a batch x (B x D fp32, row stride ldx) and the shift K = shift[D] (fp32),
+ *     sum[d] += sum_b (x[b][d] - K[d]),   cross[i * D + j] += sum_b (x[b][i] - K[i]) (x[b][j] - K[j])     (both fp64, caller-zeroed)
+ * init_shift != 0: K is first SET to this batch's column mean (the first batch of a data set).  The per-batch products are exact fp32
+ * MFMA chains over b, the cross-batch sums fp64: mu = K + sum / n, sigma = (cross - sum sum^T / n) / (n - 1). */
+int wu_feature_stats_update(const float* x, int ldx, int B, int D, float* shift, int init_shift, double* sum, double* cross, void* stream);
+
 /* layout helpers for the module boundary: NHWC `dtype` <-> NCHW fp32 (feature maps returned by
  * SNDisc.forward, disc.py:38; gradients flowing back into them). */
 int wu_nhwc_to_nchw_f32(const void* x, int ldx, float* y_nchw, int N, int H, int W, int C, int dtype, void* stream);

@@ -103,6 +103,13 @@ SIGNATURES = {
     "wu_image_workspace_bytes": (SZ, [I, I, I]),
     "wu_image_geometry": (I, [P, P, P, SZ, P, P, I, I, I, I, P]),
     "wu_image_color_jitter": (I, [P, P, P, P, I, I, P]),
+    "wu_conv_kxk_packed_bytes": (SZ, [I, I, I, I, I]),
+    "wu_pack_conv_kxk": (I, [P, P, I, I, I, I, I, I, P]),
+    "wu_conv_kxk_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "wu_pool3x3_fwd": (I, [P, I, P, I, I, I, I, I, I, I, I, I, P]),
+    "wu_global_avgpool_fwd": (I, [P, I, P, I, I, I, I, I, I, P]),
+    "wu_inception_input": (I, [P, I, I, I, I, F, F, I, P, I, I, I, I, I, P]),
+    "wu_feature_stats_update": (I, [P, I, I, I, P, I, P, P, P]),
     "wu_prof_begin": (I, [ctypes.c_uint, I]),
     "wu_prof_query": (I, [I, POINTER(c_int), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "wu_prof_end": (I, []),

@@ -1,0 +1,175 @@
+"""FID and Inception Score on the HIP InceptionV3 (the reference's eval/fid_score.py and eval/inception_score.py).
+
+    python -m wu.fid PATH1 PATH2 --weights pt_inception-2015-12-05-6726825d.pth [--dims 2048] [--batch-size 50] [--precision fp32|bf16]
+
+Each PATH is a directory of ``.jpg`` / ``.png`` images of one size or a ``.npz`` file with ``mu`` / ``sigma`` (fid_score.py's format, in
+both directions: ``FIDStatistics.save_npz`` writes it).  The weight file is the user's (pytorch-fid's FID Inception weights); nothing is
+downloaded.
+
+Feature statistics never leave the GPU per batch: ``FIDStatistics.update`` runs the network and adds the batch's shifted first and second
+moments into fp64 device accumulators (wu_feature_stats_update); ``finalize`` turns them into ``mu`` and the unbiased ``sigma``
+(np.cov(rowvar=False)).  The Frechet distance itself (a matrix square root of a D x D product) runs on the host in float64 with scipy.
+"""
+import argparse
+import os
+import pathlib
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib
+from .inception import InceptionV3, global_avgpool
+from .layout import precision_code, stream_ptr
+
+
+class FIDStatistics:
+    """Running mean / covariance of InceptionV3 features (the first requested block of ``model``: pool3 by default).
+
+    ``update(images, value_range=(0, 1))``: (N, 3, H, W) float32 in ``value_range`` or (N, H, W, 3) uint8 on the GPU.  Spatial blocks
+    (dims 64 / 192 / 768) are averaged over H x W first, as fid_score.py's adaptive_avg_pool2d does."""
+
+    def __init__(self, model):
+        self.model = model
+        self.n = 0
+        self._sum = self._cross = self._shift = None
+
+    def update(self, images, value_range=(0, 1)):
+        feat = self.model(images, value_range=value_range)[0]
+        n, c, h, w = feat.shape
+        if h * w != 1 or feat.dtype != torch.float32:
+            feat = global_avgpool(feat, precision_code(self.model.precision))
+        else:
+            feat = feat.permute(0, 2, 3, 1).reshape(n, c)          # the (N, 1, 1, C) buffer itself
+        self.update_features(feat)
+
+    def update_features(self, feats):
+        """Add a batch of feature rows (B, D) float32 on the GPU."""
+        if not feats.is_cuda or feats.dtype != torch.float32 or feats.dim() != 2 or feats.stride(1) != 1:
+            raise ValueError("FIDStatistics.update_features: expected a (B, D) float32 CUDA tensor with unit column stride")
+        b, d = feats.shape
+        first = self._sum is None
+        if first:
+            self._sum = torch.zeros(d, dtype=torch.float64, device=feats.device)
+            self._cross = torch.zeros(d, d, dtype=torch.float64, device=feats.device)
+            self._shift = torch.zeros(d, dtype=torch.float32, device=feats.device)
+        elif d != self._sum.numel():
+            raise ValueError(f"FIDStatistics: feature width {d} differs from the first batch's {self._sum.numel()}")
+        _lib.call("wu_feature_stats_update", feats.data_ptr(), feats.stride(0), b, d, self._shift.data_ptr(), 1 if first else 0,
+                  self._sum.data_ptr(), self._cross.data_ptr(), stream_ptr())
+        self.n += b
+
+    def finalize(self):
+        """(mu, sigma) float64 numpy: the sample mean and the unbiased sample covariance of every row seen."""
+        if self.n < 2:
+            raise ValueError(f"FIDStatistics: need at least 2 feature rows, have {self.n}")
+        k = self._shift.double().cpu().numpy()
+        s = self._sum.cpu().numpy()
+        cross = self._cross.cpu().numpy()
+        m = s / self.n
+        mu = k + m
+        sigma = (cross - self.n * np.outer(m, m)) / (self.n - 1)
+        return mu, sigma
+
+    def save_npz(self, path):
+        mu, sigma = self.finalize()
+        np.savez(path, mu=mu, sigma=sigma)
+
+
+def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """d^2 = ||mu1 - mu2||^2 + Tr(sigma1 + sigma2 - 2 sqrt(sigma1 sigma2)), float64 (fid_score.py's semantics: scipy's sqrtm of the
+    product; the eps * I offset retry when it is not finite; a ValueError when the imaginary part of the diagonal exceeds 1e-3)."""
+    from scipy import linalg
+    mu1, mu2 = np.atleast_1d(mu1), np.atleast_1d(mu2)
+    sigma1, sigma2 = np.atleast_2d(sigma1), np.atleast_2d(sigma2)
+    assert mu1.shape == mu2.shape, "Training and test mean vectors have different lengths"
+    assert sigma1.shape == sigma2.shape, "Training and test covariances have different dimensions"
+    diff = mu1 - mu2
+    covmean, _ = linalg.sqrtm(sigma1.dot(sigma2), disp=False)
+    if not np.isfinite(covmean).all():
+        print(f"fid calculation produces singular product; adding {eps} to diagonal of cov estimates")
+        offset = np.eye(sigma1.shape[0]) * eps
+        covmean = linalg.sqrtm((sigma1 + offset).dot(sigma2 + offset))
+    if np.iscomplexobj(covmean):
+        if not np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3):
+            raise ValueError(f"Imaginary component {np.max(np.abs(covmean.imag))}")
+        covmean = covmean.real
+    return float(diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean))
+
+
+def inception_score(logits_or_probs, splits=1, is_logits=None):
+    """exp(mean_x KL(p(y|x) || p(y))) per split of the N rows; returns (mean, std) over the splits (inception_score.py).
+    ``is_logits``: None = probabilities if every row is non-negative and sums to 1 (to 1e-3), else logits (softmax in float64)."""
+    a = logits_or_probs.detach().cpu().double().numpy() if torch.is_tensor(logits_or_probs) else np.asarray(logits_or_probs, dtype=np.float64)
+    if is_logits is None:
+        is_logits = not (np.all(a >= 0) and np.allclose(a.sum(axis=1), 1.0, atol=1e-3))
+    if is_logits:
+        e = np.exp(a - a.max(axis=1, keepdims=True))
+        p = e / e.sum(axis=1, keepdims=True)
+    else:
+        p = a / a.sum(axis=1, keepdims=True)           # scipy.stats.entropy normalises its arguments
+    n = p.shape[0]
+    scores = []
+    for k in range(splits):
+        part = p[k * (n // splits):(k + 1) * (n // splits)]
+        py = part.mean(axis=0)
+        py = py / py.sum()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            kl = np.where(part > 0, part * np.log(part / py), 0.0).sum(axis=1)
+        scores.append(np.exp(kl.mean()))
+    return float(np.mean(scores)), float(np.std(scores))
+
+
+# ----------------------------------------------------------------------------------------------
+# command line (fid_score.py)
+# ----------------------------------------------------------------------------------------------
+def image_files(path):
+    p = pathlib.Path(path)
+    return sorted(list(p.glob("*.jpg")) + list(p.glob("*.png")))
+
+
+def statistics_of_path(path, model, batch_size):
+    """(mu, sigma) of a .npz file or of the images in a directory (uint8 batches straight to the GPU)."""
+    if path.endswith(".npz"):
+        with np.load(path) as f:
+            return f["mu"][:], f["sigma"][:]
+    from PIL import Image
+    files = image_files(path)
+    if not files:
+        raise RuntimeError(f"no .jpg / .png images in {path}")
+    stats = FIDStatistics(model)
+    for i in range(0, len(files), batch_size):
+        batch = np.stack([np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8) for f in files[i:i + batch_size]])
+        stats.update(torch.from_numpy(batch).cuda())
+    return stats.finalize()
+
+
+def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32"):
+    for p in paths:
+        if not os.path.exists(p):
+            raise RuntimeError(f"Invalid path: {p}")
+    model = None
+    if not all(p.endswith(".npz") for p in paths):
+        model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], precision=precision)
+        model.load_state_dict(torch.load(weights, map_location="cpu"))
+    m1, s1 = statistics_of_path(paths[0], model, batch_size)
+    m2, s2 = statistics_of_path(paths[1], model, batch_size)
+    return calculate_frechet_distance(m1, s1, m2, s2)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m wu.fid", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                                 description="Frechet Inception Distance between two image directories / .npz statistics files")
+    ap.add_argument("path", type=str, nargs=2, help="directories of images or .npz statistics files")
+    ap.add_argument("--weights", required=True, help="pytorch-fid FID Inception weights (pt_inception-2015-12-05-*.pth)")
+    ap.add_argument("--batch-size", type=int, default=50)
+    ap.add_argument("--dims", type=int, default=2048, choices=list(InceptionV3.BLOCK_INDEX_BY_DIM))
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
+    args = ap.parse_args(argv)
+    fid = calculate_fid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision)
+    print(f"FID: {fid}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
