@@ -419,6 +419,71 @@ int wu_image_geometry(const uint8_t* src, const void* geo, void* workspace, size
  * with Pillow's arithmetic; then (dst_nchw != NULL) ToTensor + Normalize(0.5, 0.5) into (N,3,S,S) fp32. */
 int wu_image_color_jitter(uint8_t* img_u8, const float* factors, const int* order, float* dst_nchw, int N, int S, void* stream);
 
+/* ---- JPEG decoding (dataset.py:64-67, 92-96, 128-129, 148-149: Image.open(path).convert('RGB') in every loader) -------------
+ * Baseline JPEG in two halves.  The HOST half (marker parsing, Huffman decoding) is plain re-entrant C++: no global state, no
+ * allocation, callable from many threads at once and without a GPU.  The DEVICE half (dequantisation, 8x8 inverse DCT, chroma
+ * upsampling, YCbCr -> RGB, zero padding into the batch) is two kernel launches for a whole batch.  The arithmetic is libjpeg's
+ * default path (islow IDCT, fancy upsampling, jdcolor tables), so the bytes equal Pillow's.
+ *
+ * Decoded natively: 8-bit sequential Huffman (SOF0, SOF1), one interleaved scan, greyscale or YCbCr (JFIF marker, or Adobe marker
+ * with transform 1, or neither and component ids 1, 2, 3) with luma sampling 1x1 / 2x1 / 2x2 and chroma 1x1, restart intervals.
+ * Everything else is REPORTED (supported = 0 and a reason), never guessed at. */
+#define WU_JPEG_OK 0
+#define WU_JPEG_NOT_JPEG 1       /* no SOI: another format */
+#define WU_JPEG_CORRUPT 2        /* truncated or inconsistent header */
+#define WU_JPEG_PROGRESSIVE 3    /* SOF2 */
+#define WU_JPEG_ARITHMETIC 4     /* SOF9..15, DAC */
+#define WU_JPEG_PRECISION 5      /* 12-bit samples */
+#define WU_JPEG_LOSSLESS 6       /* lossless / hierarchical frames */
+#define WU_JPEG_COLORSPACE 7     /* CMYK, YCCK, RGB-tagged, two components */
+#define WU_JPEG_QTABLE16 8       /* 16-bit quantisation table */
+#define WU_JPEG_SAMPLING 9       /* 4:4:0, 4:1:1, sub-sampled luma ... */
+#define WU_JPEG_MULTISCAN 10     /* components spread over several scans */
+#define WU_JPEG_MAGNITUDE 11     /* set by the entropy stage: a block exceeds the IDCT's overflow bound */
+#define WU_JPEG_MODE_GREY 0
+#define WU_JPEG_MODE_444 1
+#define WU_JPEG_MODE_H2V1 2      /* 4:2:2 */
+#define WU_JPEG_MODE_H2V2 3      /* 4:2:0 */
+typedef struct wu_jpeg_info {
+    long long coef_bytes;            /* coefficient storage the image needs: total_blocks * 64 int16 */
+    int height, width, ncomp, mode;
+    int hs[3], vs[3], tq[3], td[3], ta[3];   /* sampling factors, quantisation / DC / AC table ids per component */
+    int restart_interval;            /* in MCUs, 0 = none */
+    int mcus_x, mcus_y;
+    int blocks_w[3], blocks_h[3];    /* blocks per row / rows of each component plane (MCU-padded) */
+    int total_blocks;
+    int supported, reason;
+    int scan_offset;                 /* first byte of the entropy-coded data */
+    int dht_off[8], dqt_off[4];      /* byte offsets of the table bodies inside the file (DC 0-3, AC 0-3; 0 = absent) */
+    int max_block_l1;                /* written by the entropy stage: max over blocks of sum |c * q| */
+    int reserved;
+} wu_jpeg_info;
+size_t wu_jpeg_info_bytes(void);
+/* Walks the markers up to SOS.  Returns 0 whenever `info` was filled; a file that cannot be decoded natively has
+ * info->supported == 0 and info->reason set. */
+int wu_jpeg_parse(const uint8_t* data, size_t nbytes, wu_jpeg_info* info);
+/* Huffman-decodes the scan of a file wu_jpeg_parse reported supported into caller-owned memory: `coef` receives
+ * info->total_blocks blocks of 64 int16 QUANTISED coefficients in natural (row-major) order, plane of component 0 first, blocks
+ * of a plane in raster order; `qtab_out` receives 3 tables of 64 uint16 in natural order (unused ones filled with 1).
+ * Returns 0, or 1 when a block's sum |c * q| exceeds the bound under which the 16- / 32-bit IDCT arithmetic cannot overflow
+ * (reason WU_JPEG_MAGNITUDE: decode such a file elsewhere), or a negative code with a message for corrupt data (bad Huffman code
+ * or table, coefficient index past 63, bad restart sequence, premature marker or end of data, buffer too small). */
+int wu_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, wu_jpeg_info* info, int16_t* coef, size_t coef_capacity_bytes,
+                           uint16_t* qtab_out);
+int wu_jpeg_max_block_l1(void);
+/* Device reconstruction of a batch.  coef_dev: the images' coefficient blocks; image n starts at block desc[n].first_block, a
+ * multiple of 32.  desc_dev: N records of wu_jpeg_desc_bytes() (= 64) bytes:
+ *     int32 first_block, h, w, mode, bw_y, bh_y, bw_c, bh_c, first_tile, nblocks, pad[6];
+ * tile_image_dev[t] = image of IDCT tile t (32 blocks; image n owns tiles first_tile .. first_tile + ceil(nblocks / 32) - 1);
+ * qtab_dev: N x 3 x 64 uint16.  workspace: wu_jpeg_workspace_bytes(32 * n_tiles) bytes (the uint8 component planes).
+ * out_u8 (N, Hmax, Wmax, 3): RGB inside each image's h x w, zero outside.  Stream-ordered, no allocation, no synchronisation.
+ * The caller builds the descriptors from wu_jpeg_parse results only; nothing here reads them on the host. */
+size_t wu_jpeg_desc_bytes(void);
+size_t wu_jpeg_workspace_bytes(long long total_blocks);
+int wu_jpeg_reconstruct(const int16_t* coef_dev, const void* desc_dev, const int* tile_image_dev, const uint16_t* qtab_dev,
+                        void* workspace, size_t workspace_bytes, uint8_t* out_u8, int N, int Hmax, int Wmax, int n_tiles,
+                        void* stream);
+
 /* ---- InceptionV3 forward for FID / Inception Score (eval/fid_score.py, eval/inception.py, eval/inception_score.py) ---------------------
  * pytorch-fid's FID InceptionV3 and torchvision's Inception3 in eval mode: every BasicConv2d is conv (no bias) + BatchNorm(eps 1e-3) + ReLU,
  * folded by the caller into one conv with an fp32 bias.  Forward only; no atomics, every result is deterministic.

@@ -103,7 +103,14 @@ SIGNATURES = {
     "wu_image_workspace_bytes": (SZ, [I, I, I]),
     "wu_image_geometry": (I, [P, P, P, SZ, P, P, I, I, I, I, P]),
     "wu_image_color_jitter": (I, [P, P, P, P, I, I, P]),
-    "wu_conv_kxk_packed_bytes": (SZ, [I, I, I, I, I]),
+    "wu_jpeg_info_bytes": (SZ, []),
+    "wu_jpeg_parse": (I, [P, SZ, P]),
+    "wu_jpeg_entropy_decode": (I, [P, SZ, P, P, SZ, P]),
+    "wu_jpeg_max_block_l1": (I, []),
+    "wu_jpeg_desc_bytes": (SZ, []),
+    "wu_jpeg_workspace_bytes": (SZ, [ctypes.c_longlong]),
+    "wu_jpeg_reconstruct": (I, [P, P, P, P, P, SZ, P, I, I, I, I, P]),
+    "wu_conv_kxk_packed_bytes":(SZ, [I, I, I, I, I]),
     "wu_pack_conv_kxk": (I, [P, P, I, I, I, I, I, I, P]),
     "wu_conv_kxk_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "wu_pool3x3_fwd": (I, [P, I, P, I, I, I, I, I, I, I, I, I, P]),

@@ -128,8 +128,9 @@ def image_files(path):
     return sorted(list(p.glob("*.jpg")) + list(p.glob("*.png")))
 
 
-def statistics_of_path(path, model, batch_size):
-    """(mu, sigma) of a .npz file or of the images in a directory (uint8 batches straight to the GPU)."""
+def statistics_of_path(path, model, batch_size, gpu_decode=False):
+    """(mu, sigma) of a .npz file or of the images in a directory (uint8 batches straight to the GPU).  gpu_decode: read the files
+    through wu.jpeg.GPUJpegDecoder instead of the per-file Pillow loop -- the same uint8 batch, hence the same statistics."""
     if path.endswith(".npz"):
         with np.load(path) as f:
             return f["mu"][:], f["sigma"][:]
@@ -138,13 +139,25 @@ def statistics_of_path(path, model, batch_size):
     if not files:
         raise RuntimeError(f"no .jpg / .png images in {path}")
     stats = FIDStatistics(model)
+    if gpu_decode:
+        from .jpeg import GPUJpegDecoder
+        dec = GPUJpegDecoder()
+        try:
+            for i in range(0, len(files), batch_size):
+                batch, sizes = dec.decode_batch(files[i:i + batch_size])
+                if any(s != sizes[0] for s in sizes):
+                    raise ValueError(f"images of different sizes in {path}: {sorted(set(sizes))}")       # np.stack's refusal below
+                stats.update(batch)
+        finally:
+            dec.close()
+        return stats.finalize()
     for i in range(0, len(files), batch_size):
         batch = np.stack([np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8) for f in files[i:i + batch_size]])
         stats.update(torch.from_numpy(batch).cuda())
     return stats.finalize()
 
 
-def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32"):
+def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False):
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError(f"Invalid path: {p}")
@@ -152,8 +165,8 @@ def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precisio
     if not all(p.endswith(".npz") for p in paths):
         model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], precision=precision)
         model.load_state_dict(torch.load(weights, map_location="cpu"))
-    m1, s1 = statistics_of_path(paths[0], model, batch_size)
-    m2, s2 = statistics_of_path(paths[1], model, batch_size)
+    m1, s1 = statistics_of_path(paths[0], model, batch_size, gpu_decode)
+    m2, s2 = statistics_of_path(paths[1], model, batch_size, gpu_decode)
     return calculate_frechet_distance(m1, s1, m2, s2)
 
 
@@ -165,8 +178,9 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=50)
     ap.add_argument("--dims", type=int, default=2048, choices=list(InceptionV3.BLOCK_INDEX_BY_DIM))
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--gpu-decode", action="store_true", help="decode the image files with wu.jpeg.GPUJpegDecoder (HIP kernels) instead of Pillow")
     args = ap.parse_args(argv)
-    fid = calculate_fid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision)
+    fid = calculate_fid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode)
     print(f"FID: {fid}")
     return 0
 

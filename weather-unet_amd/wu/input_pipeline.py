@@ -6,8 +6,9 @@
                                 -> ToTensor -> Normalize
     test                     :  Resize((S, S)) -> ToTensor -> Normalize
 
-JPEG decoding stays on the host (dataset.py:63,91: PIL ``Image.open``); what arrives here is the decoded RGB batch, one padded
-``(N, Hmax, Wmax, 3)`` uint8 tensor plus the true ``(h, w)`` of every image.  The kernels (csrc/image.hip) reproduce Pillow's
+JPEG decoding (dataset.py:63,91: PIL ``Image.open``) is ``wu.jpeg.GPUJpegDecoder`` -- Huffman decoding on host threads, the rest
+in HIP kernels -- and ``wu.data.JpegBatchLoader`` ties files, decoder and this pipeline together; what arrives here is the decoded RGB
+batch, one padded ``(N, Hmax, Wmax, 3)`` uint8 tensor plus the true ``(h, w)`` of every image.  The kernels (csrc/image.hip) reproduce Pillow's
 arithmetic bit for bit -- two-pass fixed-point bilinear resample, 16.16 fixed-point nearest rotation, ImageEnhance blends -- so
 the output equals what the reference's DataLoader workers would have produced for the same random draws; the draws themselves
 (``draw``) follow torchvision 0.3's ``get_params`` (uniform angle, log-uniform aspect ratio with 10 attempts and the central-crop
