@@ -331,11 +331,13 @@ if __name__ == "__main__":
         (gen_case, ("b2_64_soft", 2, 64, True, 1, True)),
         (gen_case, ("b1_32_soft", 1, 32, True, 2, True)),
         (gen_case, ("b3_96x_onehot", 3, 96, False, 3, False)),
+        (gen_case, ("b1_224_soft", 1, 224, True, 6, True)),            # the reference's default crop (t_cls_train.py:20): ragged conv tiles on every level
         (gen_train_case, ("train_b2_64", 2, 64, 4)),
         (gen_default_init_case, ("default_init_b2_128", 2, 128, 0)),
         (gen_default_init_case, ("default_init_b2_64", 2, 64, 5)),
         (gen_disc, ("b2_64", 2, 64, 0)),
         (gen_disc, ("b3_128", 3, 128, 1)),
+        (gen_disc, ("b2_224", 2, 224, 9)),                             # 224 -> 112 -> 56 -> 28 -> 14: a 14 x 14 output map
         (gen_disc_default_init, ("default_init_b2_64", 2, 64, 7)),      # round 3
         (gen_checkpoint, ("b2_64", 2, 64, 11)),
         (gen_eval_train_mode, ("dtrain_b3_32", 3, 32, 8)),

@@ -37,7 +37,7 @@ def _make_d(nc, seed, precision):
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("tag", ["c1_b2_128_onehot", "b2_64_soft", "b1_32_soft", "b3_96x_onehot"])
+@pytest.mark.parametrize("tag", ["c1_b2_128_onehot", "b2_64_soft", "b1_32_soft", "b3_96x_onehot", "b1_224_soft"])
 def test_cunet_forward_golden(golden_dir, tag, precision):
     g = np.load(os.path.join(golden_dir, f"cunet_{tag}.npz"))
     batch, size, soft, seed, nc = [int(v) for v in g["meta"]]
@@ -204,7 +204,7 @@ def test_cunet_train_mode_dropout(precision):
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("tag", ["b2_64", "b3_128"])
+@pytest.mark.parametrize("tag", ["b2_64", "b3_128", "b2_224"])
 def test_sndisc_golden(golden_dir, tag, precision):
     g = np.load(os.path.join(golden_dir, f"sndisc_{tag}.npz"))
     batch, size, soft, seed, nc = [int(v) for v in g["meta"]]

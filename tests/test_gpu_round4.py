@@ -477,7 +477,7 @@ def test_stride2_conv_on_the_gathered_row_pipeline(shape):
     (2, 64, 64, 64),       # the network's own form (64 -> 64, weights resident in LDS), interior tiles only
     (3, 64, 40, 48),       # ragged: a half-empty bottom tile row and a half-empty right tile column
     (1, 192, 32, 96),      # six K chunks per tile (weights re-fetched), three column tiles
-    (33, 64, 32, 32),      # more tiles than one pass of a small grid: the deferred stores of several tiles per workgroup
+    (33, 64, 32, 32),      # 66 tiles: one per workgroup on a whole chip, 13 or 14 per workgroup (their deferred stores) on the grid of 5 below
 ])
 def test_conv_relu_head_fused_vs_two_launches(shape):
     """y must be BIT-IDENTICAL to the plain conv's (same K loop, same epilogue); the head agrees with the stand-alone fp32 head kernel on the
@@ -510,6 +510,19 @@ def test_conv_relu_head_fused_vs_two_launches(shape):
     assert (out.double().cpu() - want).abs().max().item() < 2e-6
     assert (out - out_ref).abs().max().item() < 2e-6
     assert torch.equal(out, out2)
+    # ... and walked: 5 persistent workgroups (option 10), every one of them several tiles
+    ntiles = n * -(-h // 16) * -(-w // 32)
+    if ntiles >= 15:
+        try:
+            _lib.call("wu_set_option", 10, 5)
+            assert _lib.load().wu_cu_count() == 5
+            y3 = torch.full((n, h, w, 64), float("nan"), dtype=bf, device=dev).permute(0, 3, 1, 2)
+            out3 = torch.full((n, 3, h, w), float("nan"), device=dev)
+            K.conv3x3_relu_head(x, wf, bias, y3, hw_, hb, out3)
+            torch.cuda.synchronize()
+        finally:
+            _lib.call("wu_set_option", 10, 0)
+        assert torch.equal(y3.float(), y_ref.float()) and torch.equal(out3, out)
 
 
 def test_unet_forward_with_and_without_the_fused_head():
