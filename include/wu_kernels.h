@@ -484,6 +484,42 @@ int wu_jpeg_reconstruct(const int16_t* coef_dev, const void* desc_dev, const int
                         void* workspace, size_t workspace_bytes, uint8_t* out_u8, int N, int Hmax, int Wmax, int n_tiles,
                         void* stream);
 
+/* ---- JPEG encoding (inference/inf_transfer_c.py:119-120, inf_transfer_e.py:141-142, inf_1year_signals.py:105: save_image(x, '....jpg',
+ * normalize=True), i.e. one Pillow Image.save(path) per output image with Pillow's defaults) -------------------------------------
+ * Baseline JPEG (SOF0, one interleaved scan, the Annex K Huffman tables, no restart markers), YCbCr 4:2:0 or 4:4:4, quality 1..100,
+ * encoded for a whole batch in five kernel launches whatever N and the image sizes: colour conversion + chroma downsampling + forward
+ * DCT + quantisation, per-block Huffman bit counts with a prefix sum, bit packing, 0xFF counting, byte stuffing + framing.  The
+ * arithmetic is libjpeg's default compress path (jccolor / jcsample / jfdctint "islow" / jcdctmgr / jccoefct / jchuff) in integers, so
+ * every file equals the one Pillow writes, byte for byte.  The header functions are host-only and work without a GPU. */
+#define WU_JPEG_ENC_U8 2         /* sample type of the source besides WU_F32 / WU_BF16 */
+#define WU_JPEG_ENC_420 0        /* chroma subsampling */
+#define WU_JPEG_ENC_444 1
+size_t wu_jpeg_enc_header_bytes(void);      /* 623: SOI, JFIF APP0, two DQT, SOF0, four DHT, SOS */
+/* Writes that header for an h x w image; returns the byte count (> 0) or a negative code with a message. */
+int wu_jpeg_enc_header(int h, int w, int quality, int subsampling, uint8_t* out, size_t capacity);
+/* The two quantisation tables of `quality` (luma, chroma; 64 uint16 each, natural order): Annex K scaled as libjpeg does. */
+int wu_jpeg_enc_qtables(int quality, uint16_t* out128);
+/* Per-image descriptor (16 bytes): int32 h, w, capacity, pad.  `capacity`: bytes the image's entropy-coded data may take, at most
+ * cap_max.  An image that needs more is NOT truncated: its result is (0, 1). */
+size_t wu_jpeg_enc_desc_bytes(void);
+/* Caller-owned workspace for a batch of N images of at most Hmax x Wmax (0 for a shape that cannot be encoded); the byte distance
+ * between two images' files in `out`; and (tests, tools) the workspace's sections: out8 = byte offsets of the coefficient blocks
+ * (int16, 64 per block in zig-zag order, scan order, image n at block n * blocks_max), the per-block bit offsets inside their 256-block
+ * tile, the tile totals, (bits, overflow) per image, the raw bit streams (image n at n * raw_stride), the 0xFF counts per 4 KiB
+ * chunk; then blocks_max and raw_stride. */
+size_t wu_jpeg_enc_workspace_bytes(int N, int Hmax, int Wmax, int subsampling, long long cap_max);
+size_t wu_jpeg_enc_out_stride(long long cap_max);
+int wu_jpeg_enc_workspace_layout(int N, int Hmax, int Wmax, int subsampling, long long cap_max, long long* out8);
+/* Encodes the batch.  Sample (n, c, y, x) of the source is element src[n * sn + c * sc + y * sy + x * sx] of type `dtype`; float
+ * samples become bytes as x * 255 (in the tensor's precision), clamped to [0, 255], truncated.  Image n covers y < desc[n].h,
+ * x < desc[n].w; nothing outside is read.  qtab_dev: what wu_jpeg_enc_qtables wrote; hdr_dev: image n's header at n * hdr_stride.
+ * Image n's file starts at out + n * wu_jpeg_enc_out_stride(cap_max); result_dev[2n] = its byte count, result_dev[2n + 1] = 1 when
+ * it did not fit its capacity (count 0, encode it elsewhere).  Stream-ordered: no allocation, no synchronisation. */
+int wu_jpeg_enc_encode(const void* src, int dtype, long long sn, long long sc, long long sy, long long sx, const void* desc_dev,
+                       const uint16_t* qtab_dev, const uint8_t* hdr_dev, int hdr_stride, void* workspace, size_t workspace_bytes,
+                       uint8_t* out, size_t out_bytes, int* result_dev, int N, int Hmax, int Wmax, int subsampling, long long cap_max,
+                       void* stream);
+
 /* ---- InceptionV3 forward for FID / Inception Score (eval/fid_score.py, eval/inception.py, eval/inception_score.py) ---------------------
  * pytorch-fid's FID InceptionV3 and torchvision's Inception3 in eval mode: every BasicConv2d is conv (no bias) + BatchNorm(eps 1e-3) + ReLU,
  * folded by the caller into one conv with an fp32 bias.  Forward only; no atomics, every result is deterministic.

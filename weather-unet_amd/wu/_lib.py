@@ -110,6 +110,14 @@ SIGNATURES = {
     "wu_jpeg_desc_bytes": (SZ, []),
     "wu_jpeg_workspace_bytes": (SZ, [ctypes.c_longlong]),
     "wu_jpeg_reconstruct": (I, [P, P, P, P, P, SZ, P, I, I, I, I, P]),
+    "wu_jpeg_enc_header_bytes": (SZ, []),
+    "wu_jpeg_enc_header": (I, [I, I, I, I, P, SZ]),
+    "wu_jpeg_enc_qtables": (I, [I, P]),
+    "wu_jpeg_enc_desc_bytes": (SZ, []),
+    "wu_jpeg_enc_workspace_bytes": (SZ, [I, I, I, I, ctypes.c_longlong]),
+    "wu_jpeg_enc_out_stride": (SZ, [ctypes.c_longlong]),
+    "wu_jpeg_enc_workspace_layout": (I, [I, I, I, I, ctypes.c_longlong, P]),
+    "wu_jpeg_enc_encode": (I, [P, I, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, P, P, I, P, SZ, P, SZ, P, I, I, I, I, ctypes.c_longlong, P]),
     "wu_conv_kxk_packed_bytes":(SZ, [I, I, I, I, I]),
     "wu_pack_conv_kxk": (I, [P, P, I, I, I, I, I, I, P]),
     "wu_conv_kxk_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),

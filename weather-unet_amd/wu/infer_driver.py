@@ -10,6 +10,11 @@
   loop on GPU tensors; ``signal_sweep`` the same loop over arbitrary conditioning rows (``inf_transfer_e.py:136-143``),
   ``transfer_rows`` the one-row-per-image call of ``inf_1year_signals.py:98-107``, ``axis_sweep`` the conditioning
   schedule of ``demo.py:67-82``; ``normalize_minmax`` / ``to_uint8`` are save_image's arithmetic, done on the GPU.
+* Writing: every one of those scripts ends in ``save_image(output, '....jpg', normalize=True)`` -- one Pillow ``Image.save`` per
+  image.  ``save_images`` is that call for a batch: min-max normalisation on the GPU, then ``wu.jpeg_enc.GPUJpegEncoder`` for
+  ``.jpg`` / ``.jpeg`` paths (the files are encoded on the GPU, byte for byte what Pillow writes; only the compressed bytes cross to
+  the host) and Pillow for any other format.  ``class_sweep_to_dir`` is the whole loop of ``inf_transfer_c.py:114-121`` with its
+  file names.
 """
 import glob
 import os
@@ -55,7 +60,7 @@ def normalize_minmax(images, eps=1e-5):
 
 def to_uint8(images01):
     """The byte image save_image writes (torchvision <0.4: ``grid.mul(255).clamp(0, 255).byte()`` -- truncation, no +0.5),
-    NHWC uint8 on the GPU, ready for a host-side encoder."""
+    NHWC uint8 on the GPU.  (``save_images`` does not need it: the JPEG encoder applies the same arithmetic to the float batch.)"""
     return images01.mul(255).clamp_(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
 
@@ -113,3 +118,78 @@ def axis_sweep(transfer, batch, pred, thetas, alpha=1.0, graphed=None):
             per_axis.append(_run(transfer, batch, c.contiguous(), graphed))
         frames.append(torch.stack(per_axis))
     return torch.stack(frames)
+
+
+_default_encoder = None
+
+
+def _encoder(images):
+    """One shared GPUJpegEncoder with Pillow's defaults (quality 75, 4:2:0), created on first use."""
+    global _default_encoder
+    if _default_encoder is None or _default_encoder.device != images.device:
+        from .jpeg_enc import GPUJpegEncoder
+        _default_encoder = GPUJpegEncoder(device=images.device)
+    return _default_encoder
+
+
+def _pillow_save(arg):
+    from PIL import Image
+    rgb, path = arg
+    Image.fromarray(rgb).save(path)
+
+
+def _save_images_async(images, paths, normalize, encoder):
+    """Launch the writing of one batch; returns Futures still to be waited for (the Pillow formats are written before it returns)."""
+    paths = [os.fspath(p) for p in paths]
+    if images.dim() != 4 or images.shape[1] != 3 or len(paths) != images.shape[0]:
+        raise ValueError(f"save_images: a (B,3,H,W) batch and B paths, got {tuple(images.shape)} and {len(paths)} paths")
+    x = normalize_minmax(images.float()) if normalize else images
+    jpg = [i for i, p in enumerate(paths) if p.lower().endswith((".jpg", ".jpeg"))]
+    other = [i for i in range(len(paths)) if i not in set(jpg)]
+    pending = []
+    if jpg:
+        enc = encoder if encoder is not None else _encoder(images)
+        pending.append(enc.save_batch_async(x if len(jpg) == len(paths) else x[jpg], [paths[i] for i in jpg]))
+    if other:
+        rgb = to_uint8(x[other]).cpu().numpy()
+        for k, i in enumerate(other):
+            _pillow_save((rgb[k], paths[i]))
+    return pending
+
+
+@torch.no_grad()
+def save_images(images, paths, normalize=True, encoder=None):
+    """``[save_image(x, p, normalize=normalize) for x, p in zip(images, paths)]`` of the inference scripts for a (B, 3, H, W) batch
+    on the GPU: per-image min-max (``normalize_minmax``), then bytes as ``to_uint8`` makes them.  Paths ending in .jpg / .jpeg are
+    encoded by ``encoder`` (a ``GPUJpegEncoder``; default: a shared one with Pillow's defaults) from the float batch itself; any other
+    format is written by Pillow from ``to_uint8``.  Either way the file equals
+    ``Image.fromarray(to_uint8(normalize_minmax(x))[i]).save(path)`` byte for byte.  The files exist when this returns."""
+    for f in _save_images_async(images, paths, normalize, encoder):
+        f.result()
+    return [os.fspath(p) for p in paths]
+
+
+@torch.no_grad()
+def class_sweep_to_dir(transfer, batch, stems, src_labels, class_names, out_dir, normalize=True, graphed=None, encoder=None, ext=".jpg"):
+    """inf_transfer_c.py:114-121 down to the files: for every target class i, ``transfer(batch, onehot[i] tiled)`` and one file per
+    image j named ``{class_names[src_labels[j]]}_{stems[j]}_{class_names[i]}.jpg`` (``stems[j]``: the source file's name without
+    directory and extension, :120).  The files of class i are copied out and written in the background while the forward of class
+    i + 1 runs (at most two classes in flight); all of them exist when this returns.  Returns the paths, target class by target class."""
+    nc = len(class_names)
+    if len(stems) != batch.shape[0] or len(src_labels) != batch.shape[0]:
+        raise ValueError("class_sweep_to_dir: one stem and one source label per image")
+    os.makedirs(out_dir, exist_ok=True)
+    rows = torch.eye(nc, device=batch.device)
+    written, in_flight = [], []
+    for i in range(nc):
+        out = signal_sweep(transfer, batch, rows[i:i + 1], False, graphed)[0]
+        paths = [os.path.join(out_dir, f"{class_names[int(src_labels[j])]}_{stems[j]}_{class_names[i]}{ext}") for j in range(batch.shape[0])]
+        in_flight.append(_save_images_async(out, paths, normalize, encoder))
+        written += paths
+        if len(in_flight) > 2:
+            for f in in_flight.pop(0):
+                f.result()
+    for fs in in_flight:
+        for f in fs:
+            f.result()
+    return written
