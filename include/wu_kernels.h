@@ -277,6 +277,11 @@ int wu_adain_style_bwd_multi(int levels, const float* const* d_std, const float*
 #define WU_MAX_SPLITS 16
 int wu_adain_stats(const void* x, int ldx, float* stats, float* scratch, int N, int H, int W, int C,
                    float eps, int dtype, void* stream);
+/* The same statistics of N images, computed with the split count wu_adain_stats picks for a batch of `split_batch` images (a positive
+ * multiple of N): bit for bit what wu_adain_stats returns for these images inside a batch of that size.  The condition sweep
+ * (wu_adain_upcat_sweep_fwd) computes the bottleneck statistics once for B images and must match the repeated batch of R * B. */
+int wu_adain_stats_as_batch(const void* x, int ldx, float* stats, float* scratch, int N, int H, int W, int C,
+                            float eps, int split_batch, int dtype, void* stream);
 
 /* Fused AdaIN-apply (utils.py:49-50) -> bilinear x2 align_corners=True (cunet.py:26,60,67,74) ->
  * Dropout(p) (cunet.py:28,61,68,75) written into channels [0,C) of the concat buffer `y`
@@ -293,6 +298,16 @@ int wu_adain_stats(const void* x, int ldx, float* stats, float* scratch, int N, 
 int wu_adain_upcat_fwd(const void* x, int ldx, const float* stats, const float* y_std, const float* y_mean,
                        void* y, int ldy, int N, int H, int W, int C, float p_drop, uint64_t seed,
                        const uint64_t* seed_dev, uint8_t* mask_bits, int mask_is_input, int dtype, void* stream);
+/* Condition sweep (forward only): wu_adain_upcat_fwd over a VIRTUAL batch of N images whose sources are not repeated in memory.
+ * Output image n reads the activation x and `stats` of source image n % Bx (x: (Bx,H,W,C) ld=ldx, stats: (Bx,C,2); Bx divides N:
+ * Bx = B where one encoder output serves every conditioning row, Bx = N where the input is already per (row, image)), the style rows
+ * y_std / y_mean (N,C) of image n, and draws its dropout decisions from the element index of the virtual batch -- bit for bit what
+ * wu_adain_upcat_fwd writes for the materialised repeat, with the formulation chosen as that function chooses it.  The same launch
+ * also fills channels [C, C + Cs) of concat image n from `skip` (Bs,2H,2W,>=Cs) ld=ldskip, image n % Bs (Bs divides N; Cs == 0: no
+ * skip copy), so one launch writes the whole [upsampled | skip] row the consumer conv reads.  No keep bytes: nothing differentiates. */
+int wu_adain_upcat_sweep_fwd(const void* x, int ldx, int Bx, const float* stats, const float* y_std, const float* y_mean,
+                             const void* skip, int ldskip, int Bs, int Cs, void* y, int ldy, int N, int H, int W, int C,
+                             float p_drop, uint64_t seed, const uint64_t* seed_dev, int dtype, void* stream);
 /* Backward of the above.  dy: gradient of the concat buffer channels [0,C) (N,2H,2W) ld=lddy.
  * Produces dx (N,H,W,C) ld=lddx and d_y_std, d_y_mean (N,C) fp32.  `gtmp` (N*H*W*C elements of `dtype`) and
  * `sums` (N*C*2*(1+WU_MAX_SPLITS) floats) are caller-provided scratch.  x_gate_act != 0: dx is additionally multiplied by

@@ -311,28 +311,58 @@ template <int E> __device__ __forceinline__ void ldf(const float* __restrict__ p
     }
 }
 
-// grid: x = 256-thread chunks of one output row (W2 * C/E items), y = output rows (n, oh) (strided)
+// The condition sweep (wu_adain_upcat_sweep_fwd) runs the same two forward formulations over a VIRTUAL batch: image n of the output takes its
+// activation and statistics from source image n % Bx (the sources are not repeated in memory), its style rows and dropout counters from n, and
+// the same launch copies the skip tensor of image n % Bs into channels [C, C + Cs) of the concat row.  Both formulations are written once, as
+// kernel templates with a SWEEP switch: the arithmetic of an output element is one piece of code for both, and the plain instantiation (SWEEP =
+// false: every sweep branch folds away, `sw` is never read) keeps the instruction stream it had before the sweep existed.
 template <typename T>
+struct SweepSrc {
+    int Bx;                        // source images behind x / stats
+    const T* __restrict__ skip;    // (Bs, 2H, 2W, >= Cs) ld = ldskip, or nullptr
+    int ldskip, Bs, Cs;
+};
+
+// grid: x = 256-thread chunks of one output row (W2 * C/E items; sweep: W2 * (C + Cs)/E), y = output rows (n, oh) (strided)
+template <typename T, bool SWEEP = false>
 __global__ __launch_bounds__(256) void adain_upcat_fwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ stats,
                                        const float* __restrict__ y_std, const float* __restrict__ y_mean,
                                        T* __restrict__ y, int ldy, int N, int H, int W, int C,
                                        float sy, float sx, uint32_t thr, float keep_scale, uint64_t seed,
-                                       const uint64_t* __restrict__ seed_dev, uint8_t* __restrict__ mbits, int mask_in) {
+                                       const uint64_t* __restrict__ seed_dev, uint8_t* __restrict__ mbits, int mask_in, const SweepSrc<T> sw) {
     constexpr int E = ElemTraits<T>::kPer16B;
+    if (SWEEP) { mbits = nullptr; mask_in = 0; }     // no keep bytes in a sweep: nothing differentiates
     const int cpp = C / E, H2 = 2 * H, W2 = 2 * W;
+    const int cpt = SWEEP ? cpp + sw.Cs / E : cpp;   // 16-byte chunks of one concat pixel this launch writes
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= W2 * cpp) return;
+    if (idx >= W2 * cpt) return;
     // graph-safe per-replay seed: the captured kernel argument is frozen, the device-resident counter is not
     if (seed_dev) seed += *seed_dev;
-    const int ow = idx / cpp, ch = idx - ow * cpp;
+    const int ow = idx / cpt, ch = idx - ow * cpt;
     const Lerp lx = src_index(ow, sx, W);
     constexpr int RPT = 4;                           // consecutive output rows per thread (same image)
     const int groups = (H2 + RPT - 1) / RPT;
+    if (SWEEP && ch >= cpp) {                        // skip half of the concat row: a 16-byte copy per output pixel
+        const int cs = (ch - cpp) * E;
+        for (int gy = blockIdx.y; gy < N * groups; gy += gridDim.y) {
+            const int n = gy / groups, oh_base = (gy - n * groups) * RPT;
+            const int rows = min(RPT, H2 - oh_base);
+            uint4 q[RPT];
+#pragma unroll
+            for (int r = 0; r < RPT; ++r)
+                if (r < rows) q[r] = *(const uint4*)(sw.skip + (((size_t)(n % sw.Bs) * H2 + oh_base + r) * W2 + ow) * sw.ldskip + cs);
+#pragma unroll
+            for (int r = 0; r < RPT; ++r)
+                if (r < rows) *(uint4*)(y + (((size_t)n * H2 + oh_base + r) * W2 + ow) * ldy + C + cs) = q[r];
+        }
+        return;
+    }
     for (int gy = blockIdx.y; gy < N * groups; gy += gridDim.y) {
         const int n = gy / groups, oh_base = (gy - n * groups) * RPT;
         const int sc = n * C + ch * E;
+        const int ns = SWEEP ? n % sw.Bx : n;        // source image of the activation and its statistics
         float st[2 * E], ys[E], ym[E], ka[E], kb[E];
-        ldf<2 * E>(stats + 2 * sc, st);
+        ldf<2 * E>(stats + 2 * (SWEEP ? ns * C + ch * E : sc), st);
         ldf<E>(y_std + sc, ys);
         ldf<E>(y_mean + sc, ym);
 #pragma unroll
@@ -340,7 +370,7 @@ __global__ __launch_bounds__(256) void adain_upcat_fwd_kernel(const T* __restric
             ka[e] = st[2 * e + 1] * ys[e];
             kb[e] = ym[e] - st[2 * e] * ka[e];
         }
-        const T* b = x + (size_t)n * H * W * ldx + ch * E;
+        const T* b = x + (size_t)ns * H * W * ldx + ch * E;
         // all 4 x RPT neighbour loads are issued before any is consumed (rows past the image are clamped and skipped
         // at the store): one memory round trip per RPT output rows instead of one per row
         Lerp lys[RPT];
@@ -401,12 +431,13 @@ __global__ __launch_bounds__(256) void adain_upcat_fwd_kernel(const T* __restric
 // horizontally; every output row is then a two-term vertical blend of the current and the next reduced source row.  Per output
 // chunk: 0.75 loads instead of 4, one unpack per source value instead of one per tap.  Same values as adain_upcat_fwd_kernel up to
 // fp32 rounding order (the affine is applied before instead of after the interpolation).
-template <typename T>
+template <typename T, bool SWEEP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void adain_upcat_fwd_march_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ stats,
                                        const float* __restrict__ y_std, const float* __restrict__ y_mean,
                                        T* __restrict__ y, int ldy, int N, int H, int W, int C, int rows_per_strip, int col_tiles,
                                        float sy, float sx, uint32_t thr, float keep_scale, uint64_t seed,
-                                       const uint64_t* __restrict__ seed_dev, uint8_t* __restrict__ mbits, int mask_in) {
+                                       const uint64_t* __restrict__ seed_dev, uint8_t* __restrict__ mbits, int mask_in, const SweepSrc<T> sw) {
+    if (SWEEP) { mbits = nullptr; mask_in = 0; }                       // no keep bytes in a sweep: nothing differentiates
     constexpr int E = ElemTraits<T>::kPer16B;
     constexpr int LP = 64 / E, PP = 256 / LP;
     const int tid = threadIdx.x;
@@ -431,12 +462,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     if (seed_dev) seed += *seed_dev;
     const int r0 = strip * rows_per_strip, r1 = min(H2, r0 + rows_per_strip);
     if (r0 >= r1) return;
+    if (SWEEP && c0 >= C) {
+        // sweep: channel groups past C / 64 (grid x = (C + Cs) / 64) copy the skip tensor of image n % Bs into channels [C, C + Cs) of the thread's
+        // two columns; two rows of loads are in flight before their stores
+        const int cs = c0 - C;
+        const T* sb = sw.skip + (size_t)(n % sw.Bs) * H2 * W2 * sw.ldskip + cs;
+        T* yb = y + (size_t)n * H2 * W2 * ldy + C + cs;
+        for (int r = r0; r < r1; r += 2) {
+            const bool r2 = r + 1 < r1;
+            const size_t p00 = (size_t)r * W2 + j0, p10 = p00 + W2;
+            uint4 q00, q01 = {}, q10 = {}, q11 = {};
+            q00 = *(const uint4*)(sb + p00 * sw.ldskip);
+            if (v1) q01 = *(const uint4*)(sb + (p00 + 1) * sw.ldskip);
+            if (r2) q10 = *(const uint4*)(sb + p10 * sw.ldskip);
+            if (r2 && v1) q11 = *(const uint4*)(sb + (p10 + 1) * sw.ldskip);
+            *(uint4*)(yb + p00 * ldy) = q00;
+            if (v1) *(uint4*)(yb + (p00 + 1) * ldy) = q01;
+            if (r2) *(uint4*)(yb + p10 * ldy) = q10;
+            if (r2 && v1) *(uint4*)(yb + (p10 + 1) * ldy) = q11;
+        }
+        return;
+    }
+    const int ns = SWEEP ? n % sw.Bx : n;                               // source image of the activation and its statistics
     // AdaIN affine of this chunk (utils.py:49-50 folded), with the dropout keep-scale folded in
     float ka[E], kb[E];
     {
         float st[2 * E], ys[E], ym[E];
         const int sc = n * C + c0;
-        ldf<2 * E>(stats + 2 * sc, st);
+        ldf<2 * E>(stats + 2 * (SWEEP ? ns * C + c0 : sc), st);
         ldf<E>(y_std + sc, ys);
         ldf<E>(y_mean + sc, ym);
         const float ds = thr < 0x10000u ? keep_scale : 1.f;
@@ -458,7 +511,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         w0[k] = (lx0.i0 == cb + k ? lx0.l0 : 0.f) + (lx0.i1 == cb + k && lx0.i1 != lx0.i0 ? lx0.l1 : 0.f) + (lx0.i1 == lx0.i0 && lx0.i0 == cb + k ? lx0.l1 : 0.f);
         w1[k] = (lx1.i0 == cb + k ? lx1.l0 : 0.f) + (lx1.i1 == cb + k && lx1.i1 != lx1.i0 ? lx1.l1 : 0.f) + (lx1.i1 == lx1.i0 && lx1.i0 == cb + k ? lx1.l1 : 0.f);
     }
-    const T* base = x + (size_t)n * H * W * ldx + c0;
+    const T* base = x + (size_t)ns * H * W * ldx + c0;
     // reduced source rows: A = row `cur`, Bn = row `cur + 1` (two output columns each)
     float A0[E], A1[E], B0[E], B1[E];
     auto reduce_row = [&](const uint4 (&q)[3], float* o0, float* o1) __attribute__((always_inline)) {
@@ -1417,13 +1470,14 @@ extern "C" int wu_maxpool2_bwd_bits(const unsigned* gate_bits, const unsigned* s
     return 0;
 }
 
-extern "C" int wu_adain_stats(const void* x, int ldx, float* stats, float* scratch, int N, int H, int W, int C,
-                              float eps, int dtype, void* stream) {
+// `split_batch`: the batch whose split count is used (the fold order, hence the bits, follow the count)
+static int adain_stats_launch(const void* x, int ldx, float* stats, float* scratch, int N, int H, int W, int C,
+                              float eps, int split_batch, int dtype, void* stream) {
     const int esz = dtype == WU_BF16 ? 2 : 4;
     WU_REQUIRE(C % 64 == 0 && H * W > 1 && ok16(x, ldx, esz), "adain_stats: bad shape C=%d HW=%d", C, H * W);
     hipStream_t s = (hipStream_t)stream;
     const int HW = H * W;
-    int splits = cdiv(1024, N * (C / 64));
+    int splits = cdiv(1024, split_batch * (C / 64));
     if (splits > cdiv(HW, 256)) splits = cdiv(HW, 256);
     if (splits > kMaxSplits) splits = kMaxSplits;
     if (splits < 1) splits = 1;
@@ -1433,6 +1487,18 @@ extern "C" int wu_adain_stats(const void* x, int ldx, float* stats, float* scrat
     });
     WU_LAUNCH_CHECK("adain_stats");
     return 0;
+}
+
+extern "C" int wu_adain_stats(const void* x, int ldx, float* stats, float* scratch, int N, int H, int W, int C,
+                              float eps, int dtype, void* stream) {
+    return adain_stats_launch(x, ldx, stats, scratch, N, H, W, C, eps, N, dtype, stream);
+}
+
+extern "C" int wu_adain_stats_as_batch(const void* x, int ldx, float* stats, float* scratch, int N, int H, int W, int C,
+                                       float eps, int split_batch, int dtype, void* stream) {
+    WU_REQUIRE(N > 0 && split_batch >= N && split_batch % N == 0, "adain_stats_as_batch: split_batch=%d must be a positive multiple of N=%d", split_batch, N);
+    WU_REQUIRE((long long)split_batch * C < (1ll << 31), "adain_stats_as_batch: split_batch * C too large");
+    return adain_stats_launch(x, ldx, stats, scratch, N, H, W, C, eps, split_batch, dtype, stream);
 }
 
 extern "C" int wu_adain_upcat_fwd(const void* x, int ldx, const float* stats, const float* y_std, const float* y_mean,
@@ -1456,7 +1522,7 @@ extern "C" int wu_adain_upcat_fwd(const void* x, int ldx, const float* stats, co
         WU_REQUIRE((long long)col_tiles * strips < 65536, "adain_upcat_fwd: grid too large");
         DISPATCH_T(dtype, hipLaunchKernelGGL(adain_upcat_fwd_march_kernel<T>, dim3(C / 64, col_tiles * strips, N), dim3(256), 0, (hipStream_t)stream,
                                              (const T*)x, ldx, stats, y_std, y_mean, (T*)y, ldy, N, H, W, C, rows_per_strip, col_tiles, sy, sx,
-                                             keep_thr(p_drop), 1.f / (1.f - p_drop), seed, seed_dev, mask_bits, mask_is_input));
+                                             keep_thr(p_drop), 1.f / (1.f - p_drop), seed, seed_dev, mask_bits, mask_is_input, SweepSrc<T>{}));
         WU_LAUNCH_CHECK("adain_upcat_fwd (march)");
         return 0;
     }
@@ -1464,8 +1530,56 @@ extern "C" int wu_adain_upcat_fwd(const void* x, int ldx, const float* stats, co
     const dim3 grid(cdiv(2 * W * (C / (16 / esz)), 256), rows < 32768 ? rows : 32768);
     DISPATCH_T(dtype, hipLaunchKernelGGL(adain_upcat_fwd_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream,
                                          (const T*)x, ldx, stats, y_std, y_mean, (T*)y, ldy, N, H, W, C, sy, sx,
-                                         keep_thr(p_drop), 1.f / (1.f - p_drop), seed, seed_dev, mask_bits, mask_is_input));
+                                         keep_thr(p_drop), 1.f / (1.f - p_drop), seed, seed_dev, mask_bits, mask_is_input, SweepSrc<T>{}));
     WU_LAUNCH_CHECK("adain_upcat_fwd");
+    return 0;
+}
+
+extern "C" int wu_adain_upcat_sweep_fwd(const void* x, int ldx, int Bx, const float* stats, const float* y_std, const float* y_mean,
+                                        const void* skip, int ldskip, int Bs, int Cs, void* y, int ldy, int N, int H, int W, int C,
+                                        float p_drop, uint64_t seed, const uint64_t* seed_dev, int dtype, void* stream) {
+    WU_REQUIRE(dtype == WU_F32 || dtype == WU_BF16, "adain_upcat_sweep_fwd: bad dtype %d", dtype);
+    const int esz = dtype == WU_BF16 ? 2 : 4, E = 16 / esz;
+    WU_REQUIRE(x && stats && y_std && y_mean && y && N > 0 && C > 0 && H > 1 && W > 1, "adain_upcat_sweep_fwd: bad args");
+    WU_REQUIRE(Bx > 0 && N % Bx == 0, "adain_upcat_sweep_fwd: source batch Bx=%d must divide N=%d", Bx, N);
+    WU_REQUIRE(C % E == 0 && C <= ldx, "adain_upcat_sweep_fwd: C=%d must be a multiple of %d and <= ldx=%d", C, E, ldx);
+    WU_REQUIRE(Cs >= 0 && Cs % E == 0 && (long long)C + Cs <= ldy, "adain_upcat_sweep_fwd: C=%d + Cs=%d must be multiples of %d and fit ldy=%d", C, Cs, E, ldy);
+    WU_REQUIRE(Cs == 0 || (skip && Bs > 0 && N % Bs == 0 && Cs <= ldskip), "adain_upcat_sweep_fwd: skip batch Bs=%d must divide N=%d and Cs=%d <= ldskip=%d",
+               Bs, N, Cs, ldskip);
+    WU_REQUIRE(ok16(x, ldx, esz) && ok16(y, ldy, esz) && (Cs == 0 || ok16(skip, ldskip, esz)), "adain_upcat_sweep_fwd: alignment (16-byte pointers and pixel strides)");
+    WU_REQUIRE(((uintptr_t)stats % 16) == 0 && ((uintptr_t)y_std % 16) == 0 && ((uintptr_t)y_mean % 16) == 0, "adain_upcat_sweep_fwd: stats alignment");
+    WU_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "adain_upcat_sweep_fwd: p_drop");
+    WU_REQUIRE((long long)N * C < (1ll << 31) && (long long)2 * W * ((C + Cs) / E) < (1ll << 31), "adain_upcat_sweep_fwd: index range");
+    const float sy = (float)(H - 1) / (float)(2 * H - 1), sx = (float)(W - 1) / (float)(2 * W - 1);
+    const int LPv = 64 / E, PPv = 256 / LPv;
+    // the formulation and its tiling are chosen exactly as wu_adain_upcat_fwd chooses them for (N, H, W, C): same strips, same arithmetic
+    if (g_wu_opt[WU_OPT_ADAIN_FWD_MARCH] && C % 64 == 0) {
+        WU_REQUIRE(Cs % 64 == 0, "adain_upcat_sweep_fwd: Cs=%d must be a multiple of 64 where the marching formulation runs (C %% 64 == 0)", Cs);
+        const int col_tiles = cdiv(2 * W, 2 * PPv);
+        int strips = cdiv(4096, N * (C / 64) * col_tiles);
+        if (strips > cdiv(2 * H, 8)) strips = cdiv(2 * H, 8);
+        if (strips < 1) strips = 1;
+        const int rows_per_strip = cdiv(2 * H, strips);
+        strips = cdiv(2 * H, rows_per_strip);
+        WU_REQUIRE((long long)col_tiles * strips < 65536 && N < 65536, "adain_upcat_sweep_fwd: grid too large");
+        DISPATCH_T(dtype, {
+            const SweepSrc<T> sw{Bx, (const T*)skip, ldskip, Cs ? Bs : 1, Cs};
+            hipLaunchKernelGGL((adain_upcat_fwd_march_kernel<T, true>), dim3((C + Cs) / 64, col_tiles * strips, N), dim3(256), 0, (hipStream_t)stream,
+                               (const T*)x, ldx, stats, y_std, y_mean, (T*)y, ldy, N, H, W, C, rows_per_strip, col_tiles, sy, sx,
+                               keep_thr(p_drop), 1.f / (1.f - p_drop), seed, seed_dev, (uint8_t*)nullptr, 0, sw);
+        });
+        WU_LAUNCH_CHECK("adain_upcat_sweep_fwd (march)");
+        return 0;
+    }
+    const int rows = N * cdiv(2 * H, 4);
+    const dim3 grid(cdiv(2 * W * ((C + Cs) / E), 256), rows < 32768 ? rows : 32768);
+    DISPATCH_T(dtype, {
+        const SweepSrc<T> sw{Bx, (const T*)skip, ldskip, Cs ? Bs : 1, Cs};
+        hipLaunchKernelGGL((adain_upcat_fwd_kernel<T, true>), grid, dim3(256), 0, (hipStream_t)stream,
+                           (const T*)x, ldx, stats, y_std, y_mean, (T*)y, ldy, N, H, W, C, sy, sx,
+                           keep_thr(p_drop), 1.f / (1.f - p_drop), seed, seed_dev, (uint8_t*)nullptr, 0, sw);
+    });
+    WU_LAUNCH_CHECK("adain_upcat_sweep_fwd");
     return 0;
 }
 

@@ -22,7 +22,7 @@ from nets import r_double_conv
 from utils import AdaIN, BatchNorm, HalfDropout  # noqa: F401  (names the reference imports, cunet.py:3)
 from wu import functional as WF
 from wu.layout import empty_nhwc, precision_code, require_cuda, torch_dtype
-from wu.unet_graph import unet_forward
+from wu.unet_graph import unet_forward, unet_sweep
 
 _SEED_COUNTER = itertools.count(1)
 
@@ -69,6 +69,7 @@ class Conditional_UNet(nn.Module):
         self._seed_dev = None        # int64 device scalar added to the seeds inside the kernels (wu.graph_infer: per-replay masks)
         self.fused = True            # one autograd node for the whole net (wu/unet_graph.py); False = per-layer Functions
         self.grad_sink = None        # wu.ddp.GradBucketReducer.attach(): overlap gradient all-reduce with the fused backward
+        self.sweep_stats = {"encoder_images": 0, "decoder_images": 0, "chunks": 0}    # what sweep() has run so far (cumulative)
 
     def set_precision(self, precision):
         precision_code(precision)
@@ -133,3 +134,32 @@ class Conditional_UNet(nn.Module):
         x = self.dconv_up1(x)                                # :78
 
         return WF.conv1x1_tanh(x, self.conv_last.weight, self.conv_last.bias)   # :80-82
+
+    @torch.no_grad()
+    def sweep(self, x, rows, max_images=None):
+        """Every image of ``x`` (B, 3, H, W) transferred under every conditioning row of ``rows`` (R, num_classes) -- one-hot rows, soft
+        labels, standardised signals; (R, B, num_classes) gives every image its own row -- as (R, B, 3, H, W) fp32: ``[r, b]`` is image b
+        under row r.  The loop of the reference's inference and evaluation scripts (inf_transfer_c.py:114-121, inf_transfer_e.py:136-143,
+        t_cls_train.py:331-341) with the encoder, which has no dropout and does not see the condition, computed ONCE.  An extension, not in
+        the reference's interface; forward only (runs under ``torch.no_grad()``), GPU only, fused schedule only.
+
+        Semantics: over consecutive row ranges of ``Rc = max(1, max_images // B)`` rows, the result equals
+        ``self(x.repeat(Rc, 1, 1, 1), rows_chunk.repeat_interleave(B, 0))`` bit for bit.  Each chunk draws one ``_next_seed`` triple, in
+        order, as one forward call would; dropout follows ``self.training`` and honours ``dropout_seed`` / ``_seed_dev``.  With dropout
+        active the masks are therefore those of the REPEATED-BATCH forward (the element counter runs over the Rc * B images of a chunk),
+        not those of R separate calls of batch B; in eval mode there is no difference.  Caller-supplied ``dropout_masks`` are refused.
+
+        ``max_images`` (default ``wu.unet_graph.SWEEP_MAX_IMAGES`` = 128) bounds the virtual batch of a decoder chunk and with it the
+        concat buffers, the largest tensors of the pass: per virtual image 192 HW + 384 HW / 4 + 768 HW / 16 = 336 HW elements.  At
+        512 x 512 that is 168 MiB per image in bf16 (336 MiB in fp32), 21 GiB (42 GiB) for 128 images; the three buffers are live one
+        level at a time, so the peak is the level-1 buffer: 96 MiB per image in bf16, 12 GiB (24 GiB in fp32) for 128 images, next to
+        that level's conv activations.  The repeated-batch forward folds the AdaIN statistics' partial sums in an order that depends on
+        the batch (wu_adain_stats), so results for different ``max_images`` can differ in the last bits; ``max_images = B`` (one row per
+        chunk, the inference drivers' default) gives the bits of R separate forwards.  ``self.sweep_stats`` counts the encoder and
+        decoder images of all sweeps so far."""
+        require_cuda(x, "Conditional_UNet.sweep")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError(f"Conditional_UNet.sweep: x must be (B, 3, H, W) with H and W divisible by 8, got {tuple(x.shape)}")
+        if not self.fused:
+            raise ValueError("Conditional_UNet.sweep runs the fused schedule (net.fused = True)")
+        return unet_sweep(self, x, rows, max_images)

@@ -74,7 +74,9 @@ SIGNATURES = {
     "wu_adain_style_fwd_multi": (I, [I, P, P, P, P, P, P, P, I, P, I, P]),
     "wu_adain_style_bwd_multi": (I, [I, P, P, P, P, P, P, P, P, I, P, I, I, P]),
     "wu_adain_stats": (I, [P, I, P, P, I, I, I, I, F, I, P]),
+    "wu_adain_stats_as_batch": (I, [P, I, P, P, I, I, I, I, F, I, I, P]),
     "wu_adain_upcat_fwd": (I, [P, I, P, P, P, P, I, I, I, I, I, F, U64, P, P, I, I, P]),
+    "wu_adain_upcat_sweep_fwd": (I, [P, I, I, P, P, P, P, I, I, I, P, I, I, I, I, I, F, U64, P, I, P]),
     "wu_adain_upcat_bwd": (I, [P, I, P, I, P, P, P, I, P, P, P, P, I, I, I, I, F, U64, P, I, I, P]),
     "wu_dropout_mask": (I, [P, I, I, I, I, F, U64, P]),
     "wu_l1_mean_scratch_floats": (SZ, []),

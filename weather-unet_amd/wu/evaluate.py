@@ -1,0 +1,163 @@
+"""The dataset evaluation of the reference's ``eval/eval_*.py`` on top of the shared-encoder sweep (``Conditional_UNet.sweep``).
+
+* ``ClassTransferEval``      eval_class_transfer.py:106-136    every test image transferred to every class, the classifier's arg-max against
+                                                               the target class: confusion matrix + classification report
+* ``EstimatorTransferEval``  eval_estimator_transfer.py:48-61,129-130   every image transferred to every reference signal row, the estimator's
+                                                               prediction minus the row, averaged per row: mean / std of those errors
+* ``ClassifierEval``         eval_classifier_i2w.py:85-106     the classifier on the photographs themselves (no generator)
+* ``EstimatorEval``          eval_estimator.py:141-159         the estimator on the photographs themselves: mean / std of pred - target, MSE
+
+No pandas, plotting or path conventions: callers feed batches (e.g. from ``wu.data.JpegBatchLoader``).  Every ``update`` accumulates on the
+device and never synchronises with the host; ``confusion`` / ``report`` / ``result`` read the accumulators back.  The generator and the
+networks run in whatever train / eval mode they are in (the reference's scripts leave the generator's Dropout active and call ``.eval()`` on
+the classifier / estimator).  Not a hot path: torch arithmetic on a few numbers per image, no kernel of its own.
+"""
+import torch
+
+from .unet_graph import SWEEP_MAX_IMAGES
+
+
+def classification_report(confusion, names=None):
+    """``sklearn.metrics.classification_report(y_true, y_pred, output_dict=True)`` from a confusion matrix (rows = true class, columns =
+    predicted class): per class ``precision`` / ``recall`` / ``f1-score`` / ``support``, then ``accuracy``, ``macro avg`` and ``weighted avg``.
+    sklearn's conventions: an undefined ratio (a class never predicted, or without samples) counts as 0; only the classes that occur in
+    y_true or y_pred are listed and averaged; ``macro avg`` is the plain mean over them, ``weighted avg`` weighs by support."""
+    cm = torch.as_tensor(confusion).detach().to("cpu", torch.float64)
+    if cm.dim() != 2 or cm.shape[0] != cm.shape[1]:
+        raise ValueError(f"classification_report: a square confusion matrix, got {tuple(cm.shape)}")
+    nc = cm.shape[0]
+    names = [str(i) for i in range(nc)] if names is None else [str(n) for n in names]
+    tp, support, predicted = cm.diag(), cm.sum(1), cm.sum(0)
+
+    def ratio(a, b):
+        return torch.where(b > 0, a / b.clamp(min=1), torch.zeros_like(a))
+
+    prec, rec = ratio(tp, predicted), ratio(tp, support)
+    f1 = ratio(2 * prec * rec, prec + rec)
+    present = [i for i in range(nc) if support[i] > 0 or predicted[i] > 0]
+    total = support.sum()
+    out = {names[i]: {"precision": prec[i].item(), "recall": rec[i].item(), "f1-score": f1[i].item(), "support": int(support[i].item())}
+           for i in present}
+    idx = torch.tensor(present, dtype=torch.long)
+    out["accuracy"] = (tp.sum() / total).item() if total > 0 else 0.0
+    for key, wgt in (("macro avg", torch.ones(len(present), dtype=torch.float64)), ("weighted avg", support[idx])):
+        wsum = wgt.sum()
+        avg = (lambda v: ((v[idx] * wgt).sum() / wsum).item() if wsum > 0 else 0.0)
+        out[key] = {"precision": avg(prec), "recall": avg(rec), "f1-score": avg(f1), "support": int(total.item())}
+    return out
+
+
+class _Confusion:
+    """int64 nc x nc counts on the device; rows = true / target class, columns = predicted class."""
+
+    def __init__(self, num_classes, names=None):
+        self.num_classes, self.names = int(num_classes), names
+        self.cm = None
+
+    def add(self, true_idx, pred_idx):
+        nc = self.num_classes
+        if self.cm is None:
+            self.cm = torch.zeros((nc, nc), dtype=torch.int64, device=pred_idx.device)
+        flat = true_idx.to(device=pred_idx.device, dtype=torch.int64) * nc + pred_idx.to(torch.int64)
+        self.cm.view(-1).index_add_(0, flat, torch.ones_like(flat))           # no host read, unlike bincount's size query
+
+    def confusion(self):
+        nc = self.num_classes
+        return self.cm.clone() if self.cm is not None else torch.zeros((nc, nc), dtype=torch.int64)
+
+    def report(self):
+        return classification_report(self.confusion(), self.names)
+
+
+class _Rows:
+    """Rows of fp32 numbers appended on the device; mean / population std / mean square over all of them in fp64 (np.mean / np.std)."""
+
+    def __init__(self):
+        self.rows = []
+
+    def add(self, r):
+        self.rows.append(r.detach().float().reshape(-1, r.shape[-1]))
+
+    def all(self):
+        if not self.rows:
+            raise RuntimeError("no batch has been added yet")
+        return torch.cat(self.rows).double()
+
+    def result(self, mse=False):
+        a = self.all()
+        out = {"mean": a.mean(0), "std": a.std(0, unbiased=False), "count": a.shape[0]}
+        if mse:
+            out["mse"] = (a * a).mean(0)
+        return out
+
+
+def _batched(net, images, max_images):
+    """net over (M, 3, H, W) in passes of at most ``max_images`` images -> (M, k) fp32."""
+    return torch.cat([net(images[i:i + max_images]).float() for i in range(0, images.shape[0], max_images)])
+
+
+class ClassTransferEval(_Confusion):
+    """eval_class_transfer.py:106-136.  ``update(batch)`` transfers every image of the batch to every class (``transfer.sweep`` over the
+    identity rows: the encoder runs once per batch), runs ``classifier`` over the nc * B outputs in passes of at most ``max_images`` images
+    and counts arg-max of its fp32 logits (the script's Softmax does not move the arg-max) against the TARGET class.  The script's loop runs
+    ``for i in range(bs)`` over ``onehot[i]``, i.e. it assumes batch size == number of classes; this one always covers all classes, like
+    ``infer_driver.class_sweep``.  ``confusion()``: int64 (nc, nc), rows = target class, columns = predicted class; ``report()``:
+    ``classification_report`` of it.  With the generator's dropout active the masks are those of ``sweep`` (the repeated-batch forward)."""
+
+    def __init__(self, transfer, classifier, num_classes, max_images=SWEEP_MAX_IMAGES, names=None):
+        super().__init__(num_classes, names)
+        self.transfer, self.classifier, self.max_images = transfer, classifier, int(max_images)
+
+    @torch.no_grad()
+    def update(self, batch):
+        nc, b = self.num_classes, batch.shape[0]
+        fakes = self.transfer.sweep(batch, torch.eye(nc, device=batch.device), self.max_images)
+        logits = _batched(self.classifier, fakes.view(nc * b, *batch.shape[1:]), self.max_images)
+        self.add(torch.arange(nc, device=batch.device).repeat_interleave(b), logits.argmax(1))
+
+
+class EstimatorTransferEval(_Rows):
+    """eval_estimator_transfer.py:48-61,129-130.  ``update(batch, ref_signals)`` transfers every image of the batch to every row of
+    ``ref_signals`` (R, nc) (``transfer.sweep``), runs ``estimator`` over the outputs and appends, per row, the batch mean of
+    ``pred - row`` (:54-57); ``result()``: fp64 ``mean`` and population ``std`` over all appended rows (:129-130) and their ``count``."""
+
+    def __init__(self, transfer, estimator, max_images=SWEEP_MAX_IMAGES):
+        super().__init__()
+        self.transfer, self.estimator, self.max_images = transfer, estimator, int(max_images)
+
+    @torch.no_grad()
+    def update(self, batch, ref_signals):
+        ref = ref_signals.to(device=batch.device, dtype=torch.float32)
+        r, b = ref.shape[0], batch.shape[0]
+        fakes = self.transfer.sweep(batch, ref, self.max_images)
+        pred = _batched(self.estimator, fakes.view(r * b, *batch.shape[1:]), self.max_images).view(r, b, -1)
+        self.add((pred - ref.unsqueeze(1)).mean(1))
+
+
+class ClassifierEval(_Confusion):
+    """eval_classifier_i2w.py:85-106: the classifier on the photographs themselves.  ``update(batch, labels)`` counts arg-max of the fp32
+    logits against the class indices ``labels``; rows of the matrix = true class, columns = predicted class."""
+
+    def __init__(self, classifier, num_classes, names=None):
+        super().__init__(num_classes, names)
+        self.classifier = classifier
+
+    @torch.no_grad()
+    def update(self, batch, labels):
+        self.add(labels.to(batch.device), self.classifier(batch).float().argmax(1))
+
+
+class EstimatorEval(_Rows):
+    """eval_estimator.py:141-159: the estimator on the photographs themselves.  ``update(batch, signals)`` appends ``pred - signals``
+    (one row per image); ``result()``: fp64 ``mean`` / population ``std`` of those errors and ``mse``, the mean squared error per signal."""
+
+    def __init__(self, estimator):
+        super().__init__()
+        self.estimator = estimator
+
+    @torch.no_grad()
+    def update(self, batch, signals):
+        self.add(self.estimator(batch).float() - signals.to(device=batch.device, dtype=torch.float32))
+
+    def result(self):
+        return super().result(mse=True)

@@ -51,6 +51,10 @@ class GraphedUNet:
     def _params(self):
         return list(self.net.parameters())
 
+    def _forward(self):
+        """What the graph holds: one forward on the static inputs (GraphedSweep: one sweep)."""
+        return self.net(self.x, self.c)
+
     def _capture(self):
         net, dev = self.net, self.x.device
         if bool(net.training) != self.training:
@@ -63,10 +67,10 @@ class GraphedUNet:
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side), torch.no_grad():
                 for _ in range(self.warmup):   # first-use work (weight packing, attribute setup) must not be captured
-                    net(self.x, self.c)
+                    self._forward()
             torch.cuda.current_stream(dev).wait_stream(side)
             with torch.no_grad(), torch.cuda.graph(self.graph):
-                self.out = net(self.x, self.c)
+                self.out = self._forward()
                 if self.seed_counter is not None:
                     self.seed_counter.add_(4)                      # next replay: the masks of dropout_seed + 1
         finally:
@@ -106,3 +110,39 @@ class GraphedUNet:
         if self.seed_counter is None:
             raise RuntimeError("set_seed_offset: this graph was captured in eval mode (no dropout)")
         self.seed_counter.fill_(4 * int(k))
+
+
+class GraphedSweep(GraphedUNet):
+    """``Conditional_UNet.sweep`` for a static batch shape and a static number of conditioning rows in ONE hipGraph: the encoder at batch B
+    and the decoder chunk(s) at the virtual batch, a linear graph on a single stream (the sweep is forward only: nothing runs on a side
+    stream).  The input and the row VALUES are static buffers refreshed before a replay; the number of rows, ``max_images`` and the
+    train / eval mode are fixed at capture.
+
+        g = GraphedSweep(net, batch=16, size=512, rows=5)
+        out = g(x, torch.eye(5, device=x.device))          # (5, 16, 3, 512, 512), the static output tensor
+
+    ``rows``: the row count R, or a (R, nc) / (R, B, nc) tensor whose values are the first replay's.  Dropout-active graphs: replay k draws the
+    masks the eager ``net.sweep`` draws with ``dropout_seed = base_seed + k`` -- every chunk of one replay uses that seed, as the chunks of an eager
+    sweep with a fixed ``dropout_seed`` do, and the masks are those of the repeated-batch forward, not of R separate calls;
+    ``set_seed_offset`` works as in ``GraphedUNet``."""
+
+    def __init__(self, net, batch, size, rows, num_classes=None, height=None, warmup=2, base_seed=None, max_images=None):
+        nc = num_classes if num_classes is not None else net.adain1.num_classes
+        dev = next(net.parameters()).device
+        if isinstance(rows, int):
+            self.rows = torch.zeros((rows, nc), dtype=torch.float32, device=dev)
+        else:
+            self.rows = rows.detach().to(device=dev, dtype=torch.float32).clone()
+        self.max_images = max_images
+        super().__init__(net, batch, size, nc, height, warmup, base_seed)
+
+    def _forward(self):
+        return self.net.sweep(self.x, self.rows, self.max_images)
+
+    def __call__(self, x, rows=None, copy_out=False):
+        self.x.copy_(x, non_blocking=True)
+        if rows is not None:
+            if tuple(rows.shape) != tuple(self.rows.shape):
+                raise ValueError(f"GraphedSweep: captured for rows of shape {tuple(self.rows.shape)}, got {tuple(rows.shape)}")
+            self.rows.copy_(rows, non_blocking=True)
+        return self.replay(copy_out)

@@ -8,8 +8,8 @@
 * Inference: ``inference/inf_transfer_c.py:108-121`` runs, per batch, one forward per class with a tiled one-hot
   row and saves each output with ``save_image(..., normalize=True)`` (per-image min-max).  ``class_sweep`` is that
   loop on GPU tensors; ``signal_sweep`` the same loop over arbitrary conditioning rows (``inf_transfer_e.py:136-143``),
-  ``transfer_rows`` the one-row-per-image call of ``inf_1year_signals.py:98-107``, ``axis_sweep`` the conditioning
-  schedule of ``demo.py:67-82``; ``normalize_minmax`` / ``to_uint8`` are save_image's arithmetic, done on the GPU.
+  ``transfer_rows`` the one-row-per-image call of ``inf_1year_signals.py:98-107`` (``image_rows``: one image under many rows), ``axis_sweep``
+  the conditioning schedule of ``demo.py:67-82``; each takes ``shared_encoder=True`` to compute the encoder once (``Conditional_UNet.sweep``); ``normalize_minmax`` / ``to_uint8`` are save_image's arithmetic, done on the GPU.
 * Writing: every one of those scripts ends in ``save_image(output, '....jpg', normalize=True)`` -- one Pillow ``Image.save`` per
   image.  ``save_images`` is that call for a batch: min-max normalisation on the GPU, then ``wu.jpeg_enc.GPUJpegEncoder`` for
   ``.jpg`` / ``.jpeg`` paths (the files are encoded on the GPU, byte for byte what Pillow writes; only the compressed bytes cross to
@@ -68,15 +68,39 @@ def _run(transfer, batch, labels, graphed):
     return graphed(batch, labels, copy_out=True) if graphed is not None else transfer(batch, labels)
 
 
+def _sweep(transfer, batch, rows, graphed, max_images):
+    """The shared-encoder form of the loops below: ``transfer.sweep`` (or a ``GraphedSweep`` captured for this batch and row shape).
+    ``max_images=None`` here means ONE ROW PER DECODER CHUNK (the batch size): every chunk is then a forward of batch B, exactly the call the
+    loop makes -- same AdaIN split counts, same seed draws, so the same bits at every shape.  A larger value runs several rows per chunk (fewer,
+    larger launches); the result is then that of the repeated-batch forward (``Conditional_UNet.sweep``), whose instance statistics fold their
+    partial sums in an order that depends on the batch (wu_adain_stats) and can differ from the loop's in the last bits."""
+    if graphed is not None:
+        if not hasattr(graphed, "rows"):
+            raise ValueError("shared_encoder=True needs a wu.graph_infer.GraphedSweep as `graphed`, not a GraphedUNet")
+        return graphed(batch, rows, copy_out=True)
+    return transfer.sweep(batch, rows, batch.shape[0] if max_images is None else max_images)
+
+
+def _normalize_all(out, normalize):
+    return normalize_minmax(out.reshape(-1, *out.shape[-3:])).view(out.shape) if normalize else out
+
+
 @torch.no_grad()
-def signal_sweep(transfer, batch, rows, normalize=False, graphed=None):
+def signal_sweep(transfer, batch, rows, normalize=False, graphed=None, shared_encoder=False, max_images=None):
     """inference/inf_transfer_e.py:136-143 (and t_cls_train.py:336-337): for every conditioning row r of ``rows`` (R, nc) --
     soft labels, standardised weather signals, scaled one-hot rows --, ``transfer(batch, r tiled B times)``.
     Returns (R, B, 3, H, W).  ``graphed``: a ``GraphedUNet`` captured for this batch shape (one hipGraph replay per row).
     The reference never calls ``.eval()`` in these scripts, so its Dropout(0.3) is active; whether this sweep uses dropout
-    follows ``transfer.training`` exactly as there."""
+    follows ``transfer.training`` exactly as there.
+    ``shared_encoder=True``: one ``transfer.sweep`` instead of R forwards -- the encoder runs once for the batch (``graphed``: a
+    ``GraphedSweep``, best captured with ``max_images=B``).  With the default ``max_images`` (one row per decoder chunk) the result is
+    bit-identical to the loop's in eval mode, and with dropout active each chunk draws the seeds and masks the loop's call would.  A larger
+    ``max_images`` puts several rows in one chunk: the masks are then those of the repeated-batch forward (``Conditional_UNet.sweep``), not
+    those of R separate calls, and the AdaIN statistics may differ from the loop's in the last bits (see ``_sweep``)."""
     bs = batch.shape[0]
     rows = rows.to(device=batch.device, dtype=torch.float32)
+    if shared_encoder:
+        return _normalize_all(_sweep(transfer, batch, rows, graphed, max_images), normalize)
     outs = []
     for i in range(rows.shape[0]):
         labels = rows[i].unsqueeze(0).expand(bs, rows.shape[1]).contiguous()        # torch.cat([row] * bs).view(-1, nc)
@@ -86,12 +110,12 @@ def signal_sweep(transfer, batch, rows, normalize=False, graphed=None):
 
 
 @torch.no_grad()
-def class_sweep(transfer, batch, num_classes=None, normalize=False, graphed=None):
+def class_sweep(transfer, batch, num_classes=None, normalize=False, graphed=None, shared_encoder=False, max_images=None):
     """inf_transfer_c.py:114-121: for every class i, ``transfer(batch, onehot[i] tiled)`` -- ``signal_sweep`` over the rows
     of the identity.  (The script's loop runs ``for i in range(bs)`` over ``onehot[i]``, i.e. it assumes batch_size ==
-    num_classes; this sweep always covers all classes.)  Returns (num_classes, B, 3, H, W)."""
+    num_classes; this sweep always covers all classes.)  Returns (num_classes, B, 3, H, W).  ``shared_encoder``: see ``signal_sweep``."""
     nc = num_classes if num_classes is not None else transfer.adain1.num_classes
-    return signal_sweep(transfer, batch, torch.eye(nc, device=batch.device), normalize, graphed)
+    return signal_sweep(transfer, batch, torch.eye(nc, device=batch.device), normalize, graphed, shared_encoder, max_images)
 
 
 @torch.no_grad()
@@ -102,13 +126,37 @@ def transfer_rows(transfer, batch, signals, normalize=False, graphed=None):
 
 
 @torch.no_grad()
-def axis_sweep(transfer, batch, pred, thetas, alpha=1.0, graphed=None):
+def image_rows(transfer, image, signals, normalize=False, graphed=None, max_images=None):
+    """inference/inf_1year_signals.py:98-107 for ONE photograph under many conditioning rows (a year of weather records): ``image`` (3, H, W)
+    or (1, 3, H, W), ``signals`` (R, nc); returns (R, 3, H, W), row r = ``transfer(image, signals[r])``.  The encoder is computed once, the
+    decoder runs in chunks of ``max_images`` rows (default: ``Conditional_UNet.sweep``'s; ``graphed``: a ``GraphedSweep`` of batch 1 and R
+    rows).  This equals ``transfer_rows`` on the repeated image, chunk by chunk, bit for bit (in one chunk when the rows fit); with dropout
+    active the masks are those of that repeated-batch forward."""
+    if image.dim() == 3:
+        image = image.unsqueeze(0)
+    if image.dim() != 4 or image.shape[0] != 1:
+        raise ValueError(f"image_rows: one image, (3, H, W) or (1, 3, H, W), got {tuple(image.shape)}")
+    signals = signals.to(device=image.device, dtype=torch.float32)
+    out = (graphed(image, signals, copy_out=True) if graphed is not None else transfer.sweep(image, signals, max_images))[:, 0]
+    return normalize_minmax(out) if normalize else out
+
+
+@torch.no_grad()
+def axis_sweep(transfer, batch, pred, thetas, alpha=1.0, graphed=None, shared_encoder=False, max_images=None):
     """demo.py:67-82: for every angle theta and every class axis a, condition on the estimator's prediction ``pred`` (B, nc)
     with component a replaced by ``alpha * sin(theta)``:  c = onehot[a] * sin(theta) * alpha + (1 - onehot[a]) * pred.
-    Returns (T, nc, B, 3, H, W) raw outputs (the script then maps (x + 1) * 127.5 and normalises per image for the GIF)."""
+    Returns (T, nc, B, 3, H, W) raw outputs (the script then maps (x + 1) * 127.5 and normalises per image for the GIF).
+    ``shared_encoder=True``: the T * nc conditionings (each a row per image) go through one ``transfer.sweep`` -- see ``signal_sweep``."""
     nc = pred.shape[1]
     eye = torch.eye(nc, device=batch.device)
     pred = pred.to(device=batch.device, dtype=torch.float32)
+    if shared_encoder:
+        conds = []
+        for theta in thetas:
+            s = torch.sin(torch.as_tensor(float(theta), dtype=torch.float32, device=batch.device)) * alpha
+            conds.extend(eye[a].unsqueeze(0) * s + (1.0 - eye[a]).unsqueeze(0) * pred for a in range(nc))
+        out = _sweep(transfer, batch, torch.stack(conds), graphed, max_images)              # rows (T * nc, B, nc)
+        return out.view(len(conds) // nc, nc, *out.shape[1:])
     frames = []
     for theta in thetas:
         s = torch.sin(torch.as_tensor(float(theta), dtype=torch.float32, device=batch.device)) * alpha
@@ -170,19 +218,22 @@ def save_images(images, paths, normalize=True, encoder=None):
 
 
 @torch.no_grad()
-def class_sweep_to_dir(transfer, batch, stems, src_labels, class_names, out_dir, normalize=True, graphed=None, encoder=None, ext=".jpg"):
+def class_sweep_to_dir(transfer, batch, stems, src_labels, class_names, out_dir, normalize=True, graphed=None, encoder=None, ext=".jpg",
+                       shared_encoder=False, max_images=None):
     """inf_transfer_c.py:114-121 down to the files: for every target class i, ``transfer(batch, onehot[i] tiled)`` and one file per
     image j named ``{class_names[src_labels[j]]}_{stems[j]}_{class_names[i]}.jpg`` (``stems[j]``: the source file's name without
     directory and extension, :120).  The files of class i are copied out and written in the background while the forward of class
-    i + 1 runs (at most two classes in flight); all of them exist when this returns.  Returns the paths, target class by target class."""
+    i + 1 runs (at most two classes in flight); all of them exist when this returns.  Returns the paths, target class by target class.
+    ``shared_encoder=True``: all classes come from one ``transfer.sweep`` (see ``signal_sweep``), then the files are written class by class."""
     nc = len(class_names)
     if len(stems) != batch.shape[0] or len(src_labels) != batch.shape[0]:
         raise ValueError("class_sweep_to_dir: one stem and one source label per image")
     os.makedirs(out_dir, exist_ok=True)
     rows = torch.eye(nc, device=batch.device)
     written, in_flight = [], []
+    swept = _sweep(transfer, batch, rows, graphed, max_images) if shared_encoder else None
     for i in range(nc):
-        out = signal_sweep(transfer, batch, rows[i:i + 1], False, graphed)[0]
+        out = swept[i] if shared_encoder else signal_sweep(transfer, batch, rows[i:i + 1], False, graphed)[0]
         paths = [os.path.join(out_dir, f"{class_names[int(src_labels[j])]}_{stems[j]}_{class_names[i]}{ext}") for j in range(batch.shape[0])]
         in_flight.append(_save_images_async(out, paths, normalize, encoder))
         written += paths

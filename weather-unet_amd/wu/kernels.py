@@ -262,6 +262,28 @@ def adain_upcat(x, stats, y_std, y_mean, cat, p_drop, seed, want_mask_bits, seed
     return mbits
 
 
+def adain_stats_as_batch(x, eps, split_batch):
+    """``adain_stats`` of x's images with the split count of a batch of ``split_batch`` images (a multiple of x's batch): bit for bit
+    the statistics these images get inside such a batch (wu_adain_stats_as_batch)."""
+    n, c, h, w = x.shape
+    stats = torch.empty((n, c, 2), dtype=torch.float32, device=x.device)
+    scratch = torch.empty((n, c, 2 * MAX_SPLITS), dtype=torch.float32, device=x.device)
+    _lib.call("wu_adain_stats_as_batch", x.data_ptr(), nhwc_ld(x), stats.data_ptr(), scratch.data_ptr(), n, h, w, c, float(eps),
+              int(split_batch), dtype_code(x), stream_ptr())
+    return stats
+
+
+def adain_upcat_sweep(x, stats, y_std, y_mean, skip, cat, p_drop, seed, seed_dev=None):
+    """The whole ``[upsampled | skip]`` concat row of a condition sweep in one launch (wu_adain_upcat_sweep_fwd): ``cat`` holds N virtual
+    images, image n takes activation / statistics of ``x[n % x.shape[0]]``, style rows n and the skip tensor ``skip[n % skip.shape[0]]``."""
+    bx, c, h, w = x.shape
+    n = cat.shape[0]
+    _lib.call("wu_adain_upcat_sweep_fwd", x.data_ptr(), nhwc_ld(x), bx, stats.data_ptr(), y_std.data_ptr(), y_mean.data_ptr(),
+              skip.data_ptr(), nhwc_ld(skip), skip.shape[0], skip.shape[1], cat.data_ptr(), nhwc_ld(cat), n, h, w, c,
+              float(p_drop), int(seed), seed_dev.data_ptr() if seed_dev is not None else None, dtype_code(x), stream_ptr())
+    return cat
+
+
 def pack_keep_mask(mask_nchw, dtype):
     """(N, C, H2, W2) keep-mask (non-zero = keep) -> the kernels' keep-bit bytes: one byte per 16-byte channel chunk of the NHWC
     tensor, bit e = channel chunk*E + e (E = 8 bf16 / 4 fp32 elements)."""

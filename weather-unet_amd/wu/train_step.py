@@ -288,7 +288,7 @@ class WeatherTransferStep:
 
     # ------------------------------------------------------------------ t_cls_train.py:314-367 / t_est_train.py:285-332
     @torch.no_grad()
-    def evaluation(self, images, labels, ref_labels, max_images=1024):
+    def evaluation(self, images, labels, ref_labels, max_images=1024, shared_encoder=False):
         """The test-time sweep: every image of the batch transferred to every reference row's conditioning, averaged losses.
         The reference runs B passes of G / estimator / D over the B-image batch; here G and the estimator run ONE pass over
         the B*B (image, condition) pairs (chunked to ``max_images`` images).  G / D stay in whatever train / eval mode they
@@ -302,6 +302,11 @@ class WeatherTransferStep:
           then fake batch, in the reference's order (2*B forwards of B images: the same FLOPs as the batched form, more
           launches; G and the estimator, 95 % of the work, stay batched).
 
+        ``shared_encoder=True``: the generator part goes through ``Conditional_UNet.sweep`` -- the same chunks of the same
+        repeated-batch formulation, with the encoder computed once for the B images instead of once per pair; the estimator and D
+        handling are unchanged.  In eval mode the fakes are bit-identical; with dropout active the masks are, as with the flag off,
+        those of the repeated-batch form (one seed triple per chunk), not those of B separate calls.
+
         Returns (dict of device scalars g_loss_adv, g_loss_l1, g_loss_w, d_loss; fake images (B, B, 3, H, W): [i] = transfers
         to ref_labels[i])."""
         bs, nc = images.shape[0], ref_labels.shape[1]
@@ -312,11 +317,14 @@ class WeatherTransferStep:
         est = self.estimator_ if self.mode == "cls" else self.estimator                  # :338 / t_est_train.py:309
         rows = max(1, max_images // bs)
         fakes, fake_d, fake_c = [], [], []
+        swept = self.inference.sweep(images, ref_labels[:bs], max_images) if shared_encoder else None    # same chunks, one encoder pass
         for i0 in range(0, bs, rows):
             r = ref_labels[i0:i0 + rows]
             cond = r.repeat_interleave(bs, dim=0)                                        # :336 ref_labels[i] tiled B times
-            x = images.repeat(r.shape[0], 1, 1, 1)
-            f = self.inference(x, cond)                                                  # :337
+            if shared_encoder:
+                f = swept[i0:i0 + rows].view(-1, *images.shape[1:])
+            else:
+                f = self.inference(images.repeat(r.shape[0], 1, 1, 1), cond)             # :337
             fakes.append(f)
             fake_c.append(est(f))                                                        # :338
             if not d_train:

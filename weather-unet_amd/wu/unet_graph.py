@@ -424,11 +424,8 @@ class UNetFn(Function):
         return (None, dx, dys3, dym3, dys2, dym2, dys1, dym1, *flat)
 
 
-def unet_forward(net, x, c, encoder_cache=None):
-    """Run ``Conditional_UNet`` `net` through the fused graph (called by its forward).  ``encoder_cache``: a dict shared by two forwards
-    of the same input with unchanged weights -- the second reuses the first one's encoder activations (UNetFn.forward)."""
-    code = precision_code(net.precision)
-    c = c.to(device=x.device, dtype=torch.float32)
+def _styles(net, c):
+    """[y_std3, y_mean3, y_std2, y_mean2, y_std1, y_mean1] of the three AdaIN levels for the conditioning rows c (fp32, on the device)."""
     styles = []
     ads = (net.adain3, net.adain2, net.adain1)
     if STYLE_BATCHED and c.is_cuda and not c.requires_grad and all(a.num_classes <= 32 for a in ads):
@@ -440,6 +437,15 @@ def unet_forward(net, x, c, encoder_cache=None):
     else:
         for adain in ads:
             styles.extend(adain.style(c))
+    return styles
+
+
+def unet_forward(net, x, c, encoder_cache=None):
+    """Run ``Conditional_UNet`` `net` through the fused graph (called by its forward).  ``encoder_cache``: a dict shared by two forwards
+    of the same input with unchanged weights -- the second reuses the first one's encoder activations (UNetFn.forward)."""
+    code = precision_code(net.precision)
+    c = c.to(device=x.device, dtype=torch.float32)
+    styles = _styles(net, c)
     params, packed = [], []
     for name in BLOCKS:
         blk = getattr(net, name)
@@ -457,3 +463,126 @@ def unet_forward(net, x, c, encoder_cache=None):
     meta = (code, float(p), seeds, float(net.adain3.eps), packed, getattr(net, "grad_sink", None), inj,
             getattr(net, "_seed_dev", None), encoder_cache)
     return UNetFn.apply(meta, x, *styles, *params)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# condition sweep: one encoder pass, the decoder once per conditioning row (forward only)
+# ------------------------------------------------------------------------------------------------------------------------------
+SWEEP_MAX_IMAGES = 128       # default virtual batch of one decoder chunk (Conditional_UNet.sweep documents the buffers this implies)
+
+
+def sweep_chunks(num_rows, batch, max_images=None):
+    """The consecutive row ranges [(r0, r1), ...] a sweep of ``num_rows`` conditioning rows over ``batch`` images is evaluated in:
+    ``max(1, max_images // batch)`` rows per chunk, the last one possibly shorter."""
+    if num_rows < 1 or batch < 1:
+        raise ValueError(f"sweep: needs at least one row and one image, got {num_rows} rows and {batch} images")
+    rc = max(1, int(SWEEP_MAX_IMAGES if max_images is None else max_images) // batch)
+    return [(r0, min(num_rows, r0 + rc)) for r0 in range(0, num_rows, rc)]
+
+
+def sweep_plan(net, num_rows, batch, max_images=None):
+    """[(r0, r1, (seed3, seed2, seed1)), ...]: the chunks of a sweep with the dropout seeds of each -- one ``_next_seed`` triple per chunk,
+    drawn in chunk order, exactly what one forward call per chunk draws."""
+    return [(r0, r1, tuple(net._next_seed(k) for k in (3, 2, 1))) for r0, r1 in sweep_chunks(num_rows, batch, max_images)]
+
+
+def unet_sweep(net, x, rows, max_images=None):
+    """``Conditional_UNet.sweep``: every image of ``x`` (B, 3, H, W) under every conditioning row of ``rows`` -- (R, nc), or (R, B, nc) with a
+    row per image -- as (R, B, 3, H, W) fp32.  Chunk by chunk (``sweep_chunks``) the result is, bit for bit, ``net(x.repeat(Rc, 1, 1, 1),
+    rows_chunk.repeat_interleave(B, 0))``, but the encoder (cunet.py:45-54: no dropout, blind to the condition) runs ONCE at batch B for the
+    whole sweep and writes no gate / arg-max bits; the decoder runs at the virtual batch Rc * B on the unchanged conv launchers, and one
+    ``wu_adain_upcat_sweep_fwd`` launch per level writes the whole [upsampled | skip] concat row (no repeated tensors, no torch copies).  The
+    bottleneck statistics are computed once for the B encoder outputs with the split count of the chunk's Rc * B images.
+    Adds to ``net.sweep_stats``: encoder_images, decoder_images, chunks."""
+    if torch.is_grad_enabled():
+        raise RuntimeError("unet_sweep is forward only: call it under torch.no_grad()")
+    code = precision_code(net.precision)
+    dt, dev = torch_dtype(code), x.device
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.float().contiguous()
+    b, _, h, w = x.shape
+    nc = net.adain1.num_classes
+    rows = rows.to(device=dev, dtype=torch.float32)
+    if rows.dim() == 2:
+        per_image = False
+    elif rows.dim() == 3 and rows.shape[1] == b:
+        per_image = True
+    else:
+        raise ValueError(f"sweep: rows must be (R, {nc}) or (R, {b}, {nc}), got {tuple(rows.shape)}")
+    if rows.shape[-1] != nc:
+        raise ValueError(f"sweep: rows must have {nc} columns, got {tuple(rows.shape)}")
+    p = net.dropout.p if net.training else 0.0
+    if p > 0 and getattr(net, "dropout_masks", None) is not None:
+        raise ValueError("sweep: caller-supplied dropout masks belong to one forward call; use forward() for them")
+    seed_dev = getattr(net, "_seed_dev", None)
+    eps = float(net.adain3.eps)
+
+    from .functional import repack_stale
+    wb, stale = {}, []
+    for name in BLOCKS:
+        blk = getattr(net, name)
+        wb[name] = (blk[0].weight, blk[0].bias, blk[2].weight, blk[2].bias, blk[0]._packed, blk[2]._packed)
+        if name != "dconv_down1":
+            stale.append((blk[0]._packed, blk[0].weight))
+        stale.append((blk[2]._packed, blk[2].weight))
+    repack_stale(stale, code)
+
+    def conv(name, j, xin, out):
+        """conv j (0 / 2) of block `name` + bias + ReLU: the launch an undifferentiated forward makes."""
+        wt = wb[name]
+        return K.conv3x3(xin, wt[4 + j // 2].get(wt[j], code)[0], wt[j + 1], out, 1, RELU)
+
+    def pool_conv(name, xin, out, pooled):
+        wt = wb[name]
+        return K.conv3x3_relu_pool(xin, wt[5].get(wt[2], code)[0], wt[3], out, pooled)[1]
+
+    # ---- encoder, once, at batch B (cunet.py:45-54) ----
+    a1 = _new(b, 64, h, w, dt, dev)
+    K.conv3x3_c3(x, wb["dconv_down1"][0].detach().contiguous(), wb["dconv_down1"][1], a1, 1, RELU, False, code)
+    conv1, conv2, conv3 = _new(b, 64, h, w, dt, dev), _new(b, 128, h // 2, w // 2, dt, dev), _new(b, 256, h // 4, w // 4, dt, dev)
+    p1 = pool_conv("dconv_down1", a1, conv1, _new(b, 64, h // 2, w // 2, dt, dev))
+    a2 = conv("dconv_down2", 0, p1, _new(b, 128, h // 2, w // 2, dt, dev))
+    p2 = pool_conv("dconv_down2", a2, conv2, _new(b, 128, h // 4, w // 4, dt, dev))
+    a3 = conv("dconv_down3", 0, p2, _new(b, 256, h // 4, w // 4, dt, dev))
+    p3 = pool_conv("dconv_down3", a3, conv3, _new(b, 256, h // 8, w // 8, dt, dev))
+    a4 = conv("dconv_down4", 0, p3, _new(b, 512, h // 8, w // 8, dt, dev))
+    b4 = conv("dconv_down4", 2, a4, _new(b, 512, h // 8, w // 8, dt, dev))
+    del a1, p1, a2, p2, a3, p3, a4
+
+    w3c = net.conv_last.weight.detach().reshape(3, 64).contiguous()
+    b_last = net.conv_last.bias.detach()
+    num_rows = rows.shape[0]
+    out = torch.empty((num_rows, b, 3, h, w), dtype=torch.float32, device=dev)
+    plan = sweep_plan(net, num_rows, b, max_images)
+    for r0, r1, seeds in plan:
+        n = (r1 - r0) * b
+        c = rows[r0:r1].reshape(n, nc) if per_image else rows[r0:r1].repeat_interleave(b, dim=0)
+        ys3, ym3, ys2, ym2, ys1, ym1 = (t.detach().float().contiguous() for t in _styles(net, c))
+        # ---- decoder at the virtual batch n (cunet.py:59-78) ----
+        cat3 = _new(n, 768, h // 4, w // 4, dt, dev)
+        K.adain_upcat_sweep(b4, K.adain_stats_as_batch(b4, eps, n), ys3, ym3, conv3, cat3, p, seeds[0], seed_dev)
+        u3a = conv("dconv_up3", 0, cat3, _new(n, 256, h // 4, w // 4, dt, dev))
+        u3b = conv("dconv_up3", 2, u3a, _new(n, 256, h // 4, w // 4, dt, dev))
+        del cat3, u3a
+        cat2 = _new(n, 384, h // 2, w // 2, dt, dev)
+        K.adain_upcat_sweep(u3b, K.adain_stats(u3b, eps), ys2, ym2, conv2, cat2, p, seeds[1], seed_dev)
+        u2a = conv("dconv_up2", 0, cat2, _new(n, 128, h // 2, w // 2, dt, dev))
+        u2b = conv("dconv_up2", 2, u2a, _new(n, 128, h // 2, w // 2, dt, dev))
+        del cat2, u2a, u3b
+        cat1 = _new(n, 192, h, w, dt, dev)
+        K.adain_upcat_sweep(u2b, K.adain_stats(u2b, eps), ys1, ym1, conv1, cat1, p, seeds[2], seed_dev)
+        u1a = conv("dconv_up1", 0, cat1, _new(n, 64, h, w, dt, dev))
+        del cat1, u2b
+        # ---- last decoder conv + head (cunet.py:78-82), straight into this chunk's rows of the result ----
+        o = out[r0:r1].view(n, 3, h, w)
+        wt = wb["dconv_up1"]
+        if HEAD_FUSED and w3c.data_ptr() % 16 == 0 and K.conv3x3_head_supported(u1a):
+            K.conv3x3_relu_head(u1a, wt[5].get(wt[2], code)[0], wt[3], None, w3c, b_last, o)
+        else:
+            K.conv1x1_tanh(conv("dconv_up1", 2, u1a, _new(n, 64, h, w, dt, dev)), w3c, b_last, o)
+        del u1a
+    stats = net.__dict__.setdefault("sweep_stats", {"encoder_images": 0, "decoder_images": 0, "chunks": 0})
+    stats["encoder_images"] += b
+    stats["decoder_images"] += num_rows * b
+    stats["chunks"] += len(plan)
+    return out
