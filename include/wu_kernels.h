@@ -535,6 +535,29 @@ int wu_jpeg_enc_encode(const void* src, int dtype, long long sn, long long sc, l
                        uint8_t* out, size_t out_bytes, int* result_dev, int N, int Hmax, int Wmax, int subsampling, long long cap_max,
                        void* stream);
 
+/* ---- PNG encoding (the '.png' variants of the same writers; lossless files for python -m wu.fid) -----------------------------------
+ * 8-bit RGB, colour type 2, no interlace, no ancillary chunks, for a whole batch in three kernel launches whatever N and the image
+ * sizes: row filters (per row the type with the smallest sum of min(r, 256 - r), ties to the smallest type number), then per
+ * wu_png_enc_segment_bytes() of an image's filtered stream one literal-only dynamic-Huffman deflate block (code lengths <= 15), or one
+ * stored block where that is not larger, every segment but the last closed by an empty stored block so that the next starts on a byte
+ * boundary; then signature, IHDR, one IDAT chunk per segment (zlib header 78 01 in the first, Adler-32 in the last), IEND, with every
+ * CRC-32 and the Adler-32 computed on the device.  No LZ77 matching: the files are larger than zlib's, and decode to the same pixels. */
+#define WU_PNG_ENC_U8 2          /* sample type of the source besides WU_F32 / WU_BF16 */
+/* Per-image descriptor (16 bytes): int32 h, w, pad, pad. */
+size_t wu_png_enc_desc_bytes(void);
+size_t wu_png_enc_segment_bytes(void);      /* 32768 */
+/* Caller-owned workspace for a batch of N images of at most Hmax x Wmax (0 for a shape that cannot be encoded), and the byte distance
+ * between two images' files in `out`: the exact worst case of an Hmax x Wmax file, every segment stored --
+ * Hmax (1 + 3 Wmax) + (5 + 12) per segment + 51 -- so a file always fits. */
+size_t wu_png_enc_workspace_bytes(int N, int Hmax, int Wmax);
+size_t wu_png_enc_out_stride(int Hmax, int Wmax);
+/* Encodes the batch.  Samples are addressed and converted as by wu_jpeg_enc_encode; image n covers y < desc[n].h, x < desc[n].w and
+ * nothing outside is read.  Image n's file starts at out + n * wu_png_enc_out_stride(Hmax, Wmax); result_dev[n] = its byte count.
+ * Stream-ordered: no allocation, no synchronisation. */
+int wu_png_enc_encode(const void* src, int dtype, long long sn, long long sc, long long sy, long long sx, const void* desc_dev,
+                      void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int N, int Hmax, int Wmax,
+                      void* stream);
+
 /* ---- InceptionV3 forward for FID / Inception Score (eval/fid_score.py, eval/inception.py, eval/inception_score.py) ---------------------
  * pytorch-fid's FID InceptionV3 and torchvision's Inception3 in eval mode: every BasicConv2d is conv (no bias) + BatchNorm(eps 1e-3) + ReLU,
  * folded by the caller into one conv with an fp32 bias.  Forward only; no atomics, every result is deterministic.

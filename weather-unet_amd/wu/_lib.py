@@ -120,6 +120,11 @@ SIGNATURES = {
     "wu_jpeg_enc_out_stride": (SZ, [ctypes.c_longlong]),
     "wu_jpeg_enc_workspace_layout": (I, [I, I, I, I, ctypes.c_longlong, P]),
     "wu_jpeg_enc_encode": (I, [P, I, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, P, P, I, P, SZ, P, SZ, P, I, I, I, I, ctypes.c_longlong, P]),
+    "wu_png_enc_desc_bytes": (SZ, []),
+    "wu_png_enc_segment_bytes": (SZ, []),
+    "wu_png_enc_workspace_bytes": (SZ, [I, I, I]),
+    "wu_png_enc_out_stride": (SZ, [I, I]),
+    "wu_png_enc_encode": (I, [P, I, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, P, SZ, P, SZ, P, I, I, I, P]),
     "wu_conv_kxk_packed_bytes":(SZ, [I, I, I, I, I]),
     "wu_pack_conv_kxk": (I, [P, P, I, I, I, I, I, I, P]),
     "wu_conv_kxk_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),

@@ -13,7 +13,8 @@
 * Writing: every one of those scripts ends in ``save_image(output, '....jpg', normalize=True)`` -- one Pillow ``Image.save`` per
   image.  ``save_images`` is that call for a batch: min-max normalisation on the GPU, then ``wu.jpeg_enc.GPUJpegEncoder`` for
   ``.jpg`` / ``.jpeg`` paths (the files are encoded on the GPU, byte for byte what Pillow writes; only the compressed bytes cross to
-  the host) and Pillow for any other format.  ``class_sweep_to_dir`` is the whole loop of ``inf_transfer_c.py:114-121`` with its
+  the host) and Pillow for any other format -- or, for ``.png`` paths, a ``wu.png_enc.GPUPngEncoder`` passed as ``png_encoder``
+  (lossless files encoded on the GPU; without one, PNG stays on Pillow).  ``class_sweep_to_dir`` is the whole loop of ``inf_transfer_c.py:114-121`` with its
   file names.
 """
 import glob
@@ -186,15 +187,18 @@ def _pillow_save(arg):
     Image.fromarray(rgb).save(path)
 
 
-def _save_images_async(images, paths, normalize, encoder):
+def _save_images_async(images, paths, normalize, encoder, png_encoder=None):
     """Launch the writing of one batch; returns Futures still to be waited for (the Pillow formats are written before it returns)."""
     paths = [os.fspath(p) for p in paths]
     if images.dim() != 4 or images.shape[1] != 3 or len(paths) != images.shape[0]:
         raise ValueError(f"save_images: a (B,3,H,W) batch and B paths, got {tuple(images.shape)} and {len(paths)} paths")
     x = normalize_minmax(images.float()) if normalize else images
     jpg = [i for i, p in enumerate(paths) if p.lower().endswith((".jpg", ".jpeg"))]
-    other = [i for i in range(len(paths)) if i not in set(jpg)]
+    png = [i for i, p in enumerate(paths) if p.lower().endswith(".png")] if png_encoder is not None else []
+    other = [i for i in range(len(paths)) if i not in set(jpg) | set(png)]
     pending = []
+    if png:
+        pending.append(png_encoder.save_batch_async(x if len(png) == len(paths) else x[png], [paths[i] for i in png]))
     if jpg:
         enc = encoder if encoder is not None else _encoder(images)
         pending.append(enc.save_batch_async(x if len(jpg) == len(paths) else x[jpg], [paths[i] for i in jpg]))
@@ -206,25 +210,28 @@ def _save_images_async(images, paths, normalize, encoder):
 
 
 @torch.no_grad()
-def save_images(images, paths, normalize=True, encoder=None):
+def save_images(images, paths, normalize=True, encoder=None, png_encoder=None):
     """``[save_image(x, p, normalize=normalize) for x, p in zip(images, paths)]`` of the inference scripts for a (B, 3, H, W) batch
     on the GPU: per-image min-max (``normalize_minmax``), then bytes as ``to_uint8`` makes them.  Paths ending in .jpg / .jpeg are
     encoded by ``encoder`` (a ``GPUJpegEncoder``; default: a shared one with Pillow's defaults) from the float batch itself; any other
     format is written by Pillow from ``to_uint8``.  Either way the file equals
-    ``Image.fromarray(to_uint8(normalize_minmax(x))[i]).save(path)`` byte for byte.  The files exist when this returns."""
-    for f in _save_images_async(images, paths, normalize, encoder):
+    ``Image.fromarray(to_uint8(normalize_minmax(x))[i]).save(path)`` byte for byte.  ``png_encoder`` (a ``wu.png_enc.GPUPngEncoder``;
+    default None: Pillow, as before) takes the paths ending in .png: those files are then encoded on the GPU as well -- lossless, the
+    same pixels, not Pillow's bytes.  The files exist when this returns."""
+    for f in _save_images_async(images, paths, normalize, encoder, png_encoder):
         f.result()
     return [os.fspath(p) for p in paths]
 
 
 @torch.no_grad()
 def class_sweep_to_dir(transfer, batch, stems, src_labels, class_names, out_dir, normalize=True, graphed=None, encoder=None, ext=".jpg",
-                       shared_encoder=False, max_images=None):
+                       shared_encoder=False, max_images=None, png_encoder=None):
     """inf_transfer_c.py:114-121 down to the files: for every target class i, ``transfer(batch, onehot[i] tiled)`` and one file per
     image j named ``{class_names[src_labels[j]]}_{stems[j]}_{class_names[i]}.jpg`` (``stems[j]``: the source file's name without
     directory and extension, :120).  The files of class i are copied out and written in the background while the forward of class
     i + 1 runs (at most two classes in flight); all of them exist when this returns.  Returns the paths, target class by target class.
-    ``shared_encoder=True``: all classes come from one ``transfer.sweep`` (see ``signal_sweep``), then the files are written class by class."""
+    ``shared_encoder=True``: all classes come from one ``transfer.sweep`` (see ``signal_sweep``), then the files are written class by class.
+    ``png_encoder``: with ``ext=".png"``, the ``GPUPngEncoder`` that writes the files (see ``save_images``); None: Pillow."""
     nc = len(class_names)
     if len(stems) != batch.shape[0] or len(src_labels) != batch.shape[0]:
         raise ValueError("class_sweep_to_dir: one stem and one source label per image")
@@ -235,7 +242,7 @@ def class_sweep_to_dir(transfer, batch, stems, src_labels, class_names, out_dir,
     for i in range(nc):
         out = swept[i] if shared_encoder else signal_sweep(transfer, batch, rows[i:i + 1], False, graphed)[0]
         paths = [os.path.join(out_dir, f"{class_names[int(src_labels[j])]}_{stems[j]}_{class_names[i]}{ext}") for j in range(batch.shape[0])]
-        in_flight.append(_save_images_async(out, paths, normalize, encoder))
+        in_flight.append(_save_images_async(out, paths, normalize, encoder, png_encoder))
         written += paths
         if len(in_flight) > 2:
             for f in in_flight.pop(0):
