@@ -558,6 +558,49 @@ int wu_png_enc_encode(const void* src, int dtype, long long sn, long long sc, lo
                       void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int N, int Hmax, int Wmax,
                       void* stream);
 
+/* ---- PNG decoding, host side (the reader of wu_png_enc_encode's files: the header parse; no device stage yet) --------------------------
+ * 8-bit RGB, colour type 2, no interlace, and the framing the encoder writes: IDAT chunk k holds the deflate data of bytes
+ * [32768 k, 32768 (k + 1)) of the filtered stream as a self-contained, byte-aligned run of deflate blocks that references nothing before
+ * its start (zlib's Z_FULL_FLUSH every wu_png_enc_segment_bytes(), pigz -i), the zlib header in front of the first, the Adler-32 behind
+ * the last.  The segments of such a file are found from the chunk headers alone and can be inflated independently of each other.
+ *
+ * wu_png_dec_parse: host only, no GPU.  Reads untrusted bytes: every length is checked against `nbytes` in 64-bit arithmetic before
+ * use.  Returns 0 whenever `info` was filled; a file that is not taken natively has info->supported == 0 and info->reason:
+ *   NOT_PNG        no signature
+ *   HEADER         no IHDR of 13 bytes with a right CRC as the first chunk, a zero size, compression / filter method not 0, interlace > 1
+ *   COLOUR_TYPE / BIT_DEPTH / INTERLACED   not colour type 2 / not 8 bits / Adam7 (tested in this order)
+ *   TOO_LARGE      height * width over `max_pixels`, or a side over 65535
+ *   CORRUPT_CHUNK  a chunk that runs past the end of the file (a truncated file, no IEND), IDAT chunks that are not consecutive, none at
+ *                  all, a critical chunk other than IHDR / IDAT / IEND (PLTE included), or a bad zlib header (CM = 8, window <= 32 KiB,
+ *                  FCHECK, no FDICT) at the start of the first IDAT
+ *   NOT_SEGMENTED  not exactly ceil(height (1 + 3 width) / 32768) IDAT chunks, a first one without room for the zlib header, a last one
+ *                  without room for the Adler-32, or one of more than wu_png_dec_max_chunk_bytes() bytes
+ * Ancillary chunks before and after the IDAT run are skipped unread; the IDAT CRCs are left to whoever inflates.  idat[2 i], idat[2 i + 1]
+ * receive offset (inside the file) and length of the i-th IDAT body for i < idat_capacity; info->n_idat counts all of them, so a caller
+ * whose list was too short calls again.  A supported file may still be a foreign one with the right chunk count by coincidence: that
+ * shows when the segments are inflated. */
+#define WU_PNG_DEC_OK 0
+#define WU_PNG_DEC_NOT_PNG 1
+#define WU_PNG_DEC_HEADER 2
+#define WU_PNG_DEC_COLOUR_TYPE 3
+#define WU_PNG_DEC_BIT_DEPTH 4
+#define WU_PNG_DEC_INTERLACED 5
+#define WU_PNG_DEC_NOT_SEGMENTED 6
+#define WU_PNG_DEC_TOO_LARGE 7
+#define WU_PNG_DEC_CORRUPT_CHUNK 8
+typedef struct wu_png_dec_info {
+    long long filtered_bytes;        /* height (1 + 3 width) */
+    int height, width;
+    int bit_depth, colour_type, interlace;
+    int n_idat;                      /* IDAT chunks in the file */
+    int n_segments;                  /* ceil(filtered_bytes / 32768) */
+    int supported, reason;
+    int reserved;
+} wu_png_dec_info;
+size_t wu_png_dec_info_bytes(void);
+size_t wu_png_dec_max_chunk_bytes(void);    /* 40960: a 32 KiB segment of 9-bit fixed-Huffman literals and some */
+int wu_png_dec_parse(const uint8_t* data, size_t nbytes, long long max_pixels, wu_png_dec_info* info, long long* idat, int idat_capacity);
+
 /* ---- InceptionV3 forward for FID / Inception Score (eval/fid_score.py, eval/inception.py, eval/inception_score.py) ---------------------
  * pytorch-fid's FID InceptionV3 and torchvision's Inception3 in eval mode: every BasicConv2d is conv (no bias) + BatchNorm(eps 1e-3) + ReLU,
  * folded by the caller into one conv with an fp32 bias.  Forward only; no atomics, every result is deterministic.

@@ -125,6 +125,9 @@ SIGNATURES = {
     "wu_png_enc_workspace_bytes": (SZ, [I, I, I]),
     "wu_png_enc_out_stride": (SZ, [I, I]),
     "wu_png_enc_encode": (I, [P, I, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, P, SZ, P, SZ, P, I, I, I, P]),
+    "wu_png_dec_info_bytes": (SZ, []),
+    "wu_png_dec_max_chunk_bytes": (SZ, []),
+    "wu_png_dec_parse": (I, [P, SZ, ctypes.c_longlong, P, P, I]),
     "wu_conv_kxk_packed_bytes":(SZ, [I, I, I, I, I]),
     "wu_pack_conv_kxk": (I, [P, P, I, I, I, I, I, I, P]),
     "wu_conv_kxk_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
