@@ -558,7 +558,7 @@ int wu_png_enc_encode(const void* src, int dtype, long long sn, long long sc, lo
                       void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int N, int Hmax, int Wmax,
                       void* stream);
 
-/* ---- PNG decoding, host side (the reader of wu_png_enc_encode's files: the header parse; no device stage yet) --------------------------
+/* ---- PNG decoding (the reader of wu_png_enc_encode's files: the header parse on the host, inflate and unfilter on the device) ---------
  * 8-bit RGB, colour type 2, no interlace, and the framing the encoder writes: IDAT chunk k holds the deflate data of bytes
  * [32768 k, 32768 (k + 1)) of the filtered stream as a self-contained, byte-aligned run of deflate blocks that references nothing before
  * its start (zlib's Z_FULL_FLUSH every wu_png_enc_segment_bytes(), pigz -i), the zlib header in front of the first, the Adler-32 behind
@@ -600,6 +600,26 @@ typedef struct wu_png_dec_info {
 size_t wu_png_dec_info_bytes(void);
 size_t wu_png_dec_max_chunk_bytes(void);    /* 40960: a 32 KiB segment of 9-bit fixed-Huffman literals and some */
 int wu_png_dec_parse(const uint8_t* data, size_t nbytes, long long max_pixels, wu_png_dec_info* info, long long* idat, int idat_capacity);
+
+/* The device stage: two launches for a batch of N parsed files, each a grid of one-wave workgroups (csrc/png_dec.hip).
+ * src_dev: the files' bytes, uploaded by the caller.  desc_dev: N descriptors of wu_png_dec_desc_bytes() (32) bytes
+ *     { long long src_off; int file_bytes, h, w, first_seg, nseg, pad; }     h = w = 0: not decoded here, the slot is zeroed, status 0
+ * seg_dev: n_segments rows of wu_png_dec_seg_bytes() (16) bytes { int image, k; uint32_t off, len; } -- the k-th IDAT body of `image` at
+ * `off` inside its file -- the rows of one image consecutive from its first_seg.  out_u8: (N, Hmax, Wmax, 3), every byte written: the
+ * image, zeros as padding, all zeros for an image with a status other than 0.  status_dev[n]: 0, or 1 chunk-crc, 2 bad-stream,
+ * 3 distance (a match reaching in front of its segment), 4 segment-size, 5 filter-type, 6 adler -- the first failing check of the first
+ * failing segment, then filter-type, then adler; at least as strict as zlib.
+ * Every buffer comes with its length in bytes and the call is refused (-1, wu_last_error) if one is smaller than N, Hmax, Wmax and
+ * n_segments require; the kernels check every descriptor and segment row against the same lengths before they follow it, so a bad row
+ * gives status 2, never an access outside a buffer.  workspace: wu_png_dec_workspace_bytes() bytes, 256-byte aligned (0: unsupported
+ * shape -- a side over 65535, more than 2^30 filtered bytes per image, more segments than N images of that size have).
+ * Stream-ordered: no allocation, no synchronisation. */
+size_t wu_png_dec_desc_bytes(void);
+size_t wu_png_dec_seg_bytes(void);
+size_t wu_png_dec_workspace_bytes(int N, int Hmax, int Wmax, long long n_segments);
+int wu_png_dec_decode(const uint8_t* src_dev, size_t src_bytes, const void* desc_dev, size_t desc_bytes, const void* seg_dev, size_t seg_bytes,
+                      int n_segments, void* workspace, size_t workspace_bytes, uint8_t* out_u8, size_t out_bytes, int* status_dev,
+                      size_t status_bytes, int N, int Hmax, int Wmax, void* stream);
 
 /* ---- InceptionV3 forward for FID / Inception Score (eval/fid_score.py, eval/inception.py, eval/inception_score.py) ---------------------
  * pytorch-fid's FID InceptionV3 and torchvision's Inception3 in eval mode: every BasicConv2d is conv (no bias) + BatchNorm(eps 1e-3) + ReLU,

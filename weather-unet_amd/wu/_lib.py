@@ -128,6 +128,10 @@ SIGNATURES = {
     "wu_png_dec_info_bytes": (SZ, []),
     "wu_png_dec_max_chunk_bytes": (SZ, []),
     "wu_png_dec_parse": (I, [P, SZ, ctypes.c_longlong, P, P, I]),
+    "wu_png_dec_desc_bytes": (SZ, []),
+    "wu_png_dec_seg_bytes": (SZ, []),
+    "wu_png_dec_workspace_bytes": (SZ, [I, I, I, ctypes.c_longlong]),
+    "wu_png_dec_decode": (I, [P, SZ, P, SZ, P, SZ, I, P, SZ, P, SZ, P, SZ, I, I, I, P]),
     "wu_conv_kxk_packed_bytes":(SZ, [I, I, I, I, I]),
     "wu_pack_conv_kxk": (I, [P, P, I, I, I, I, I, I, P]),
     "wu_conv_kxk_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),

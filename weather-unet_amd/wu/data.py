@@ -35,7 +35,7 @@ class JpegBatchLoader:
     advances the seed.  Leaving an epoch early (break, exception, ``close()``) stops and joins its background thread."""
 
     def __init__(self, paths, targets=None, batch_size=16, pipeline=None, decoder=None, shuffle=False, sample_weights=None,
-                 num_samples=None, seed=None, drop_last=False, prefetch=2):
+                 num_samples=None, seed=None, drop_last=False, prefetch=2, png_decode=False):
         self.paths = list(paths)
         if not self.paths:
             raise ValueError("JpegBatchLoader: no files")
@@ -50,6 +50,9 @@ class JpegBatchLoader:
         self.weights = None if sample_weights is None else torch.as_tensor(np.asarray(sample_weights, dtype=np.float64))
         self.num_samples = len(self.paths) if num_samples is None else int(num_samples)
         self.seed = random.SystemRandom().randrange(2 ** 31) if seed is None else int(seed)
+        if decoder is None and png_decode:                # opt-in: a directory of segmented PNGs (wu.png_enc's) inflated on the GPU
+            from .png import GPUPngDecoder
+            decoder = GPUPngDecoder()
         if decoder is None:
             from .jpeg import GPUJpegDecoder
             decoder = GPUJpegDecoder()

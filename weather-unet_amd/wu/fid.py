@@ -128,9 +128,11 @@ def image_files(path):
     return sorted(list(p.glob("*.jpg")) + list(p.glob("*.png")))
 
 
-def statistics_of_path(path, model, batch_size, gpu_decode=False):
+def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False):
     """(mu, sigma) of a .npz file or of the images in a directory (uint8 batches straight to the GPU).  gpu_decode: read the files
-    through wu.jpeg.GPUJpegDecoder instead of the per-file Pillow loop -- the same uint8 batch, hence the same statistics."""
+    through wu.jpeg.GPUJpegDecoder instead of the per-file Pillow loop; gpu_decode_png: through wu.png.GPUPngDecoder, which inflates the
+    segmented PNGs wu.png_enc writes on the GPU and hands every other file to Pillow -- the same uint8 batch, hence the same statistics.
+    Both off by default."""
     if path.endswith(".npz"):
         with np.load(path) as f:
             return f["mu"][:], f["sigma"][:]
@@ -139,9 +141,13 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False):
     if not files:
         raise RuntimeError(f"no .jpg / .png images in {path}")
     stats = FIDStatistics(model)
-    if gpu_decode:
-        from .jpeg import GPUJpegDecoder
-        dec = GPUJpegDecoder()
+    if gpu_decode or gpu_decode_png:
+        if gpu_decode_png:
+            from . import png
+            dec = png.GPUPngDecoder()
+        else:
+            from .jpeg import GPUJpegDecoder
+            dec = GPUJpegDecoder()
         try:
             for i in range(0, len(files), batch_size):
                 batch, sizes = dec.decode_batch(files[i:i + batch_size])
@@ -157,7 +163,7 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False):
     return stats.finalize()
 
 
-def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False):
+def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False):
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError(f"Invalid path: {p}")
@@ -165,8 +171,8 @@ def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precisio
     if not all(p.endswith(".npz") for p in paths):
         model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], precision=precision)
         model.load_state_dict(torch.load(weights, map_location="cpu"))
-    m1, s1 = statistics_of_path(paths[0], model, batch_size, gpu_decode)
-    m2, s2 = statistics_of_path(paths[1], model, batch_size, gpu_decode)
+    m1, s1 = statistics_of_path(paths[0], model, batch_size, gpu_decode, gpu_decode_png)
+    m2, s2 = statistics_of_path(paths[1], model, batch_size, gpu_decode, gpu_decode_png)
     return calculate_frechet_distance(m1, s1, m2, s2)
 
 
@@ -179,8 +185,10 @@ def main(argv=None):
     ap.add_argument("--dims", type=int, default=2048, choices=list(InceptionV3.BLOCK_INDEX_BY_DIM))
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--gpu-decode", action="store_true", help="decode the image files with wu.jpeg.GPUJpegDecoder (HIP kernels) instead of Pillow")
+    ap.add_argument("--gpu-decode-png", action="store_true",
+                    help="decode segmented PNG files (what wu.png_enc writes) with wu.png.GPUPngDecoder (HIP kernels); other files go to Pillow")
     args = ap.parse_args(argv)
-    fid = calculate_fid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode)
+    fid = calculate_fid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png)
     print(f"FID: {fid}")
     return 0
 
