@@ -558,6 +558,53 @@ int wu_png_enc_encode(const void* src, int dtype, long long sn, long long sc, lo
                       void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int N, int Hmax, int Wmax,
                       void* stream);
 
+/* ---- image grids and tables (torchvision.utils.make_grid in front of the writers above) ------------------------------------------------
+ * Every multi-image output of the reference is make_grid(..., normalize=True, scale_each=True) of the pinned torchvision (< 0.4):
+ * demo.py:74-82 (per angle, 1 + num_classes one-column grids side by side, the frames of the GIF), t_cls_train.py:361-378 and
+ * t_est_train.py:342 (the evaluation summary: a blank and the reference images, then one strip per image), and the tables of
+ * inf_transfer_c.py:122-123 / inf_transfer_e.py:151-156.  A table is a list of CELLS, described once on the host and uploaded; one call
+ * composes any number of cells in any number of frames of one geometry in THREE launches (csrc/grid.hip): pad fill + range reset, ranges,
+ * compose.  Per pixel, in fp32, IEEE round-to-nearest, in this order:
+ *     x = source value (bf16 widened), 0 for a blank cell;   WU_GRID_PRE: x = (x + 1) * 127.5            (demo.py:80)
+ *     WU_GRID_NORMALIZE: v = clamp(x, lo, hi);  x = (v - lo) / (hi - lo + 1e-5f)                          (make_grid's norm_ip; true division)
+ * with (lo, hi) the minimum and maximum of x over ALL cells of the cell's group (blank cells count with their zeros), or the cell's own
+ * lo / hi with WU_GRID_FIXED_RANGE (make_grid's range=; every cell of a group carries the same pair).  The ranges do not depend on the
+ * launch geometry.  NaN in a source: the range of its group and every pixel normalised by it are unspecified.
+ * Output, every byte written (pad_value where no cell lies):
+ *     WU_GRID_OUT_F32  fp32 planar (frames, 3, Hg, Wg): what make_grid returns
+ *     WU_GRID_OUT_U8   uint8 interleaved (frames, Hg, Wg, 3): x * 255, clamped to [0, 255], truncated (save_image's bytes; pad_value goes
+ *                      through the same conversion) -- the batch wu_jpeg_enc_encode / wu_png_enc_encode take as it is
+ * The descriptors live in device memory, so the kernels check them: a cell that is empty, lies outside its frame in any direction, has
+ * no source and is not blank, or normalises by a group outside [0, n_groups) is ignored -- nothing is written outside the output. */
+#define WU_GRID_BF16 1          /* flags: the source holds bf16 (else fp32) */
+#define WU_GRID_PRE 2           /*        pre-transform (x + 1) * 127.5 */
+#define WU_GRID_BLANK 4         /*        zeros, no source is read (t_cls_train.py:324,361) */
+#define WU_GRID_NORMALIZE 8     /*        normalise by the group's range (else the value is written as it is) */
+#define WU_GRID_FIXED_RANGE 16  /*        ... by this cell's lo / hi instead: no reduction */
+#define WU_GRID_OUT_F32 0
+#define WU_GRID_OUT_U8 1
+typedef struct wu_grid_cell {
+    uint64_t src;                    /* device pointer of sample (c = 0, y = 0, x = 0) */
+    long long sc, sy, sx;            /* element strides: sample (c, y, x) at src[c * sc + y * sy + x * sx] -- NCHW, channels-last and slices alike */
+    int h, w;
+    int frame, y0, x0;               /* the cell covers rows y0 .. y0 + h - 1, columns x0 .. x0 + w - 1 of its frame */
+    int group;
+    int flags;
+    float lo, hi;                    /* WU_GRID_FIXED_RANGE */
+    int reserved;
+} wu_grid_cell;
+size_t wu_grid_cell_bytes(void);     /* 72 */
+/* Caller-owned workspace (0 for counts outside 1 .. 2^20), and for tests and tools its sections as byte offsets: out2[0] = the per-group
+ * (lo, hi) fp32 pairs, group g at out2[0] + 8 g, written by the compose launch for every group a WU_GRID_NORMALIZE cell uses (zero
+ * otherwise); out2[1] = the order-preserving uint32 images the range launch reduces into. */
+size_t wu_grid_workspace_bytes(int n_cells, int n_groups);
+int wu_grid_workspace_layout(int n_cells, int n_groups, long long* out2);
+/* Composes the table.  Everything the host can know is checked before the first launch (rc < 0, wu_last_error): the counts, the geometry
+ * (frames, Hg, Wg in 1 .. 2^20), out_kind, out_bytes >= frames * Hg * Wg * 3 * element size, the workspace size, null pointers, alignment
+ * (descriptors 8, workspace and output 16 bytes).  Stream-ordered: no allocation, no synchronisation, capturable. */
+int wu_grid_compose(const void* cells_dev, int n_cells, int n_groups, void* workspace, size_t workspace_bytes, void* out, size_t out_bytes,
+                    int out_kind, int frames, int Hg, int Wg, float pad_value, void* stream);
+
 /* ---- PNG decoding (the reader of wu_png_enc_encode's files: the header parse on the host, inflate and unfilter on the device) ---------
  * 8-bit RGB, colour type 2, no interlace, and the framing the encoder writes: IDAT chunk k holds the deflate data of bytes
  * [32768 k, 32768 (k + 1)) of the filtered stream as a self-contained, byte-aligned run of deflate blocks that references nothing before
@@ -675,6 +722,7 @@ int wu_nchw_f32_to_nhwc(const float* x_nchw, void* y, int ldy, int N, int H, int
 #define WU_FAM_CONV_S2 4     /* conv3x3_mfma_kernel<T,2,false>: discriminator stride-2 forward */
 #define WU_FAM_WGRAD_S2 5    /* conv3x3_wgrad_kernel<T,2,P> */
 #define WU_FAM_CONV1X1 6     /* conv1x1_mfma_kernel<T>: pointwise convs of the estimator */
+#define WU_FAM_GRID 7        /* the three launches of wu_grid_compose (bytes: the fill only; the cells' sizes are device data) */
 int wu_prof_begin(unsigned family_mask, int max_launches);
 int wu_prof_query(int family, int* launches, double* total_ms, double* total_flops, double* total_bytes);
 int wu_prof_end(void);

@@ -15,6 +15,7 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 OPT_CONV_V2, OPT_CONV_PERSISTENT, OPT_WGRAD_V2 = 0, 1, 2
 FAM_CONV_FWD, FAM_WGRAD, FAM_CONV_DGRAD, FAM_CONV_S2, FAM_WGRAD_S2, FAM_CONV1X1 = 1, 2, 3, 4, 5, 6
+FAM_GRID = 7         # the launches of wu_grid_compose (wu/grid.py)
 FAMILY_KERNEL = {1: "conv3x3_mfma_v2_kernel (forward + data-gradient convs; generic conv3x3_mfma_kernel for fp32 / narrow images)",
                  2: "conv3x3_wgrad_v2_kernel (generic conv3x3_wgrad_kernel for fp32 / narrow images)",
                  3: "conv3x3_mfma_kernel<T,1,true> (in-kernel gated dgrad; unused by the fused graph)",
@@ -125,6 +126,10 @@ SIGNATURES = {
     "wu_png_enc_workspace_bytes": (SZ, [I, I, I]),
     "wu_png_enc_out_stride": (SZ, [I, I]),
     "wu_png_enc_encode": (I, [P, I, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, P, SZ, P, SZ, P, I, I, I, P]),
+    "wu_grid_cell_bytes": (SZ, []),
+    "wu_grid_workspace_bytes": (SZ, [I, I]),
+    "wu_grid_workspace_layout": (I, [I, I, P]),
+    "wu_grid_compose": (I, [P, I, I, P, SZ, P, SZ, I, I, I, I, F, P]),
     "wu_png_dec_info_bytes": (SZ, []),
     "wu_png_dec_max_chunk_bytes": (SZ, []),
     "wu_png_dec_parse": (I, [P, SZ, ctypes.c_longlong, P, P, I]),

@@ -16,6 +16,9 @@
   the host) and Pillow for any other format -- or, for ``.png`` paths, a ``wu.png_enc.GPUPngEncoder`` passed as ``png_encoder``
   (lossless files encoded on the GPU; without one, PNG stays on Pillow).  ``class_sweep_to_dir`` is the whole loop of ``inf_transfer_c.py:114-121`` with its
   file names.
+* Pictures of several images: the reference builds them with ``make_grid(..., normalize=True, scale_each=True)`` (demo.py:74-82, the
+  evaluation summary of t_cls_train.py:361-378).  ``save_grid`` is ``save_image`` called with a batch, ``demo_frames`` / ``save_demo`` the
+  tables and the GIF of demo.py:67-92; the composition runs on the GPU (``wu.grid``) and hands uint8 frames to the encoders.
 """
 import glob
 import os
@@ -187,12 +190,10 @@ def _pillow_save(arg):
     Image.fromarray(rgb).save(path)
 
 
-def _save_images_async(images, paths, normalize, encoder, png_encoder=None):
-    """Launch the writing of one batch; returns Futures still to be waited for (the Pillow formats are written before it returns)."""
-    paths = [os.fspath(p) for p in paths]
-    if images.dim() != 4 or images.shape[1] != 3 or len(paths) != images.shape[0]:
-        raise ValueError(f"save_images: a (B,3,H,W) batch and B paths, got {tuple(images.shape)} and {len(paths)} paths")
-    x = normalize_minmax(images.float()) if normalize else images
+def _route_async(x, paths, encoder, png_encoder, to_bytes):
+    """One batch to its files by extension: .jpg / .jpeg to ``encoder`` (default: the shared one), .png to ``png_encoder`` when one is
+    passed, anything else to Pillow from ``to_bytes(sub-batch)``, an (n, H, W, 3) uint8 batch.  ``x``: whatever the encoders take, the
+    float (B, 3, H, W) batch or finished (B, H, W, 3) uint8.  Returns Futures still to be waited for (Pillow's files are written)."""
     jpg = [i for i, p in enumerate(paths) if p.lower().endswith((".jpg", ".jpeg"))]
     png = [i for i, p in enumerate(paths) if p.lower().endswith(".png")] if png_encoder is not None else []
     other = [i for i in range(len(paths)) if i not in set(jpg) | set(png)]
@@ -200,13 +201,22 @@ def _save_images_async(images, paths, normalize, encoder, png_encoder=None):
     if png:
         pending.append(png_encoder.save_batch_async(x if len(png) == len(paths) else x[png], [paths[i] for i in png]))
     if jpg:
-        enc = encoder if encoder is not None else _encoder(images)
+        enc = encoder if encoder is not None else _encoder(x)
         pending.append(enc.save_batch_async(x if len(jpg) == len(paths) else x[jpg], [paths[i] for i in jpg]))
     if other:
-        rgb = to_uint8(x[other]).cpu().numpy()
+        rgb = to_bytes(x[other]).cpu().numpy()
         for k, i in enumerate(other):
             _pillow_save((rgb[k], paths[i]))
     return pending
+
+
+def _save_images_async(images, paths, normalize, encoder, png_encoder=None):
+    """Launch the writing of one batch; returns Futures still to be waited for (the Pillow formats are written before it returns)."""
+    paths = [os.fspath(p) for p in paths]
+    if images.dim() != 4 or images.shape[1] != 3 or len(paths) != images.shape[0]:
+        raise ValueError(f"save_images: a (B,3,H,W) batch and B paths, got {tuple(images.shape)} and {len(paths)} paths")
+    x = normalize_minmax(images.float()) if normalize else images
+    return _route_async(x, paths, encoder, png_encoder, to_uint8)
 
 
 @torch.no_grad()
@@ -251,3 +261,54 @@ def class_sweep_to_dir(transfer, batch, stems, src_labels, class_names, out_dir,
         for f in fs:
             f.result()
     return written
+
+
+def _save_u8_async(frames, paths, encoder, png_encoder):
+    """``_save_images_async`` for finished bytes: an (N, H, W, 3) uint8 batch on the GPU, routed by extension the same way."""
+    return _route_async(frames, paths, encoder, png_encoder, lambda u8: u8)
+
+
+@torch.no_grad()
+def save_grid(tensor, path, nrow=8, padding=2, normalize=False, value_range=None, scale_each=False, pad_value=0.0, encoder=None,
+              png_encoder=None):
+    """``torchvision.utils.save_image(tensor, path, nrow, padding, normalize, range, scale_each, pad_value)`` for a batch: the grid of
+    ``wu.grid.make_grid`` composed straight to the bytes ``to_uint8`` makes, then written as ``save_images`` writes: .jpg / .jpeg by
+    ``encoder`` (a ``GPUJpegEncoder``; default: the shared one), .png by ``png_encoder`` when one is passed, else -- and any other
+    format -- by Pillow.  The file exists when this returns."""
+    from . import grid
+    path = os.fspath(path)
+    u8 = grid.compose_grid(tensor, nrow, padding, normalize, value_range, scale_each, pad_value, out="uint8").unsqueeze(0)
+    for f in _save_u8_async(u8, [path], encoder, png_encoder):
+        f.result()
+    return path
+
+
+@torch.no_grad()
+def demo_frames(transfer, batch, pred, thetas, alpha=1.0, **axis_sweep_kw):
+    """demo.py:67-82 down to the tables: ``axis_sweep`` (its keywords pass through), then per angle the ``1 + nc`` one-column grids side
+    by side, every cell normalised by its own range -- all T frames composed in one call (``wu.grid.demo_tables``).  Returns
+    (T, Hg, Wg, 3) uint8 on the GPU: the input of the encoders and of ``save_demo``."""
+    from . import grid
+    return grid.demo_tables(batch, axis_sweep(transfer, batch, pred, thetas, alpha, **axis_sweep_kw), out="uint8")
+
+
+def save_demo(frames_u8, out, encoder=None, png_encoder=None, ext=".jpg", stem="frame"):
+    """Writes the frames of ``demo_frames``.  ``out`` ending in .gif: the animation of demo.py:86-92, written by Pillow from the fetched
+    bytes -- ping-pong order ``frames[0], frames[1:] + frames[1:-1][::-1]``, ``duration=1000 // T``, ``loop=0`` (palette and LZW stay on
+    the host).  Anything else is a directory: one file ``{stem}{t:04d}{ext}`` per frame through the GPU encoders, routed by ``ext`` as
+    ``save_images`` routes.  Returns the path of the GIF, or the list of files."""
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
+        raise ValueError(f"save_demo: (T, Hg, Wg, 3) uint8 frames, got {tuple(frames_u8.shape)} {frames_u8.dtype}")
+    out = os.fspath(out)
+    T = frames_u8.shape[0]
+    if out.lower().endswith(".gif"):
+        from PIL import Image
+        rgb = frames_u8.cpu().numpy()
+        imgs = [Image.fromarray(f).convert("RGB") for f in rgb]
+        imgs[0].save(out, save_all=True, append_images=imgs[1:] + imgs[1:-1][::-1], duration=1000 // T, loop=0)
+        return out
+    os.makedirs(out, exist_ok=True)
+    paths = [os.path.join(out, f"{stem}{t:04d}{ext}") for t in range(T)]
+    for f in _save_u8_async(frames_u8, paths, encoder, png_encoder):
+        f.result()
+    return paths

@@ -349,3 +349,13 @@ class WeatherTransferStep:
             "d_loss": d_loss,
         }
         return losses, fake.view(bs, bs, *images.shape[1:])
+
+    # ------------------------------------------------------------------ t_cls_train.py:361-378 / t_est_train.py:342
+    @staticmethod
+    def summary_image(images, ref_images, fakes, out="float"):
+        """The ``images/test`` picture of the evaluation: a blank and ``ref_images`` on top, below one strip ``[images[j] | fakes[0][j] ..
+        fakes[B-1][j]]`` per image, every strip min-max normalised as a whole -- ``make_grid(res_img, nrow=1, normalize=True,
+        scale_each=True)`` of :361-378, composed on the GPU (``wu.grid.summary_image``).  ``fakes``: what ``evaluation`` returned.
+        Returns fp32 (3, Hg, Wg) (``out="uint8"``: (Hg, Wg, 3) bytes) for whatever logger the training loop uses."""
+        from . import grid
+        return grid.summary_image(images, ref_images, fakes, out)
