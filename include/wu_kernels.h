@@ -710,6 +710,29 @@ int wu_feature_stats_update(const float* x, int ldx, int B, int D, float* shift,
 int wu_nhwc_to_nchw_f32(const void* x, int ldx, float* y_nchw, int N, int H, int W, int C, int dtype, void* stream);
 int wu_nchw_f32_to_nhwc(const float* x_nchw, void* y, int ldy, int N, int H, int W, int C, int dtype, void* stream);
 
+/* ---- GIF encoding (the animation of the demo tables: wu.infer_driver.save_demo(..., gif_encoder=)) ------------------------------------
+ * T frames (uint8, interleaved RGB, any non-negative element strides) become T GIF89a image blocks -- graphic control extension, image
+ * descriptor, a 256-entry local colour table, LZW data in 255-byte sub-blocks -- in five launches and one stream-ordered memset, whatever
+ * T and the frame size.  Per frame, independently: a 32768-bin histogram over the top 5 bits of each channel (count and 64-bit channel
+ * sums), median cut over the occupied bins down to at most 256 boxes (the box with the largest count x extent is cut at the median of
+ * its longest axis), palette entry = rounded mean of the box, index = the box of the pixel's bin (no dithering, no nearest-colour
+ * search); then GIF LZW with an 8-bit minimum code size over segments of wu_gif_enc_segment_pixels() indices, every segment starting
+ * from the fresh dictionary and ending in a Clear code (the last in the end-of-information code), the segments' bit strings joined at
+ * bit granularity.  All integer, deterministic: the blocks equal tests/_gif_enc_ref.py byte for byte.  The host puts `GIF89a`, the
+ * logical screen descriptor, the loop extension and the trailer around the blocks (wu/gif_enc.py). */
+size_t wu_gif_enc_segment_pixels(void);     /* 8192 */
+/* Caller-owned workspace for T frames of H x W (0 for a shape that cannot be encoded: over 65535 on a side or over 2^26 pixels), and the
+ * byte distance between two frames' blocks in `out`: the exact worst case of a block, every pixel a 12-bit code and four more codes per
+ * segment -- with nseg = ceil(H W / 8192) and P = ceil(12 (H W + 4 nseg) / 8):  8 + 10 + 768 + 1 + P + ceil(P / 255) + 1. */
+size_t wu_gif_enc_workspace_bytes(int T, int H, int W);
+size_t wu_gif_enc_block_stride(int H, int W);
+/* Encodes the frames: pixel (t, y, x), channel c at frames[t * stride_t + y * stride_y + x * stride_x + c * stride_c].  Frame t's block
+ * starts at out + t * wu_gif_enc_block_stride(H, W); result_dev[t] = its byte count.  delay_cs: the frame delay in 1/100 s (0..65535).
+ * Stream-ordered: no allocation, no synchronisation. */
+int wu_gif_enc_encode(const uint8_t* frames, long long stride_t, long long stride_y, long long stride_x, long long stride_c, void* workspace,
+                      size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int T, int H, int W, int delay_cs,
+                      void* stream);
+
 /* ---- instrumentation (bench.py roofline leg) -------------------------------------------------
  * While enabled, the launchers of the kernel families in `family_mask` (bit f = family f) bracket each
  * launch with hipEvents on the launch stream (events come from a pool created by wu_prof_begin; nothing

@@ -126,6 +126,10 @@ SIGNATURES = {
     "wu_png_enc_workspace_bytes": (SZ, [I, I, I]),
     "wu_png_enc_out_stride": (SZ, [I, I]),
     "wu_png_enc_encode": (I, [P, I, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, P, SZ, P, SZ, P, I, I, I, P]),
+    "wu_gif_enc_segment_pixels": (SZ, []),
+    "wu_gif_enc_workspace_bytes": (SZ, [I, I, I]),
+    "wu_gif_enc_block_stride": (SZ, [I, I]),
+    "wu_gif_enc_encode": (I, [P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, SZ, P, SZ, P, I, I, I, I, P]),
     "wu_grid_cell_bytes": (SZ, []),
     "wu_grid_workspace_bytes": (SZ, [I, I]),
     "wu_grid_workspace_layout": (I, [I, I, P]),

@@ -1,0 +1,184 @@
+"""GIF encoding of the demo animation (csrc/gif_enc.hip): the palette and the LZW of ``wu.infer_driver.save_demo(frames, "x.gif")`` on
+the GPU, so that what crosses to the host is the finished image blocks instead of every frame as raw RGB.
+
+Per frame, independently: a 32768-bin histogram over the top 5 bits of each channel, median cut over the occupied bins down to at most 256
+boxes, palette entry = rounded mean of its box, index = the box of the pixel's bin (no dithering, no nearest-colour search); then GIF LZW
+over segments of 8192 indices that each start from the fresh dictionary, their bit strings joined bit by bit.  Every distinct frame is
+quantised and coded ONCE; the host puts ``GIF89a``, the logical screen descriptor, the loop extension and the trailer around the blocks
+and repeats a block wherever ``order`` names its frame again (the ping-pong of demo.py names all but two frames twice).
+
+The files are NOT the bytes Pillow writes (another palette order, one unsegmented LZW): Pillow decodes them to ``palette[index]``, and they
+equal ``tests/_gif_enc_ref.encode`` byte for byte.  The output buffer is sized by the exact worst case (every pixel a 12-bit code), so there
+is no overflow and no Pillow fallback.
+
+Limitation: colours are told apart by their histogram bin, so an image with several distinct colours in one 5-bit bin is not reproduced
+exactly even if it has 256 colours or fewer (a 256-level grey ramp comes out at about 41 dB, where Pillow is exact).
+
+    enc = GPUGifEncoder()
+    data = enc.encode(frames, duration_ms=125, loop=0, order=ping_pong(T))      # frames (T, H, W, 3) uint8 on the GPU; bytes
+    enc.save(frames, "demo.gif", duration_ms=125, order=ping_pong(T))
+"""
+import os
+import struct
+import threading
+
+import torch
+
+from . import _lib
+from .jpeg import _Staging
+from .layout import stream_ptr
+
+
+def ping_pong(t):
+    """[0 .. t-1, t-2 .. 1]: the frame order of demo.py's animation."""
+    t = int(t)
+    return list(range(t)) + list(range(t - 2, 0, -1))
+
+
+def segment_pixels():
+    """Indices per LZW segment.  Host only."""
+    return int(_lib.load().wu_gif_enc_segment_pixels())
+
+
+def block_stride(h, w):
+    """The exact worst case of an h x w image block: the distance between two frames' blocks in the output buffer.  Host only."""
+    n = int(_lib.load().wu_gif_enc_block_stride(int(h), int(w)))
+    if n == 0:
+        raise ValueError(f"gif_enc: cannot encode {h} x {w} (at most 65535 on a side and 2^26 pixels)")
+    return n
+
+
+class DeviceResult:
+    """Result of GPUGifEncoder.launch: the image blocks on the device (frame t at ``out[t * block_stride:]``) and their byte counts in
+    ``result``."""
+    def __init__(self, out, result, workspace, frames, t, h, w, stride):
+        self.out, self.result, self.workspace, self.frames = out, result, workspace, frames
+        self.t, self.h, self.w, self.block_stride = t, h, w, stride
+
+
+class GPUGifEncoder:
+    """Animated-GIF encoder on the GPU.
+
+    ``encode(frames, duration_ms, loop, order)`` = ``fetch(launch(frames), duration_ms, loop, order)``.  ``launch`` queues one memset and
+    five kernels on the CURRENT stream and never synchronises; it holds no per-geometry device state, so it can be captured in a
+    ``torch.cuda.graph`` as it is.  ``fetch`` does one small device-to-host copy of the T byte counts, then one copy of exactly the used
+    bytes into a pinned staging buffer, and assembles the file: header, the blocks in ``order`` with the frame delay written into each,
+    trailer.
+
+    Staging-buffer rule (the decoder's): a buffer is refilled only after the event recorded behind the copy that wrote it has completed.
+
+    ``frames``: (T, H, W, 3) uint8 on the GPU, any non-negative strides (what ``wu.grid.demo_tables(..., out="uint8")`` returns).
+    """
+    def __init__(self, device="cuda", max_staging=4):
+        self.device = torch.device(device)
+        self.max_staging = int(max_staging)
+        self._lock = threading.Lock()
+        self._staging = []
+        self.stats = {"frames": 0, "bytes": 0}
+        self._lib = _lib.load()
+        self.segment_pixels = int(self._lib.wu_gif_enc_segment_pixels())
+
+    def close(self):
+        with self._lock:
+            self._staging.clear()
+
+    # ---- staging buffers (the rule of GPUJpegDecoder._acquire) ----
+    def _acquire(self, nbytes):
+        with self._lock:
+            free = [s for s in self._staging if not s.held]
+            for s in free:
+                if s.tensor.numel() >= nbytes and (s.event is None or s.event.query()):
+                    s.held = True
+                    return s
+            if len(self._staging) >= self.max_staging and free:
+                s = free[0]
+                self._staging.remove(s)
+                if s.event is not None:
+                    s.event.synchronize()
+            s = _Staging(max(int(nbytes * 1.25), 1 << 20), torch.cuda.is_available())
+            s.held = True
+            self._staging.append(s)
+            return s
+
+    def _release(self, s):
+        with self._lock:
+            s.held = False
+
+    # ---- device stage ----
+    def launch(self, frames):
+        """The kernels on the current stream; returns a DeviceResult."""
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
+            what = f"{tuple(frames.shape)} {frames.dtype}" if isinstance(frames, torch.Tensor) else type(frames).__name__
+            raise ValueError(f"GPUGifEncoder: frames must be a (T, H, W, 3) uint8 tensor, got {what}")
+        if not frames.is_cuda or not torch.cuda.is_available() or self.device.type != "cuda":
+            raise RuntimeError("GPUGifEncoder: the encoder runs HIP kernels on an MI355X only -- there is no CPU fallback "
+                               "(wu.gif_enc.block_stride / segment_pixels / ping_pong are the host-only entry points)")
+        t, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        if t < 1 or h < 1 or w < 1:
+            raise ValueError("GPUGifEncoder: no frames")
+        st, sy, sx, sc = frames.stride()
+        if min(st, sy, sx, sc) < 0:
+            raise ValueError("GPUGifEncoder: negative strides")
+        stride = int(self._lib.wu_gif_enc_block_stride(h, w))
+        ws_bytes = int(self._lib.wu_gif_enc_workspace_bytes(t, h, w))
+        if stride == 0 or ws_bytes == 0:
+            raise ValueError(f"GPUGifEncoder: cannot encode {t} frames of {h} x {w} (at most 65535 on a side and 2^26 pixels)")
+        with torch.cuda.device(frames.device):
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=frames.device)
+            out = torch.empty(t * stride, dtype=torch.uint8, device=frames.device)
+            result = torch.empty(t, dtype=torch.int32, device=frames.device)
+            _lib.call("wu_gif_enc_encode", frames.data_ptr(), st, sy, sx, sc, ws.data_ptr(), ws.numel(), out.data_ptr(), out.numel(),
+                      result.data_ptr(), t, h, w, 0, stream_ptr())
+        return DeviceResult(out, result, ws, frames, t, h, w, stride)
+
+    # ---- host stage ----
+    def fetch(self, res, duration_ms, loop=0, order=None):
+        """bytes: the GIF file of a launched batch of frames, shown in ``order`` (default 0 .. T-1) for ``duration_ms`` each (GIF counts
+        1/100 s: ``duration_ms // 10``), repeated ``loop`` times (0: for ever; None: no loop extension, shown once)."""
+        delay = int(duration_ms) // 10
+        if not 0 <= delay <= 65535:
+            raise ValueError(f"GPUGifEncoder: duration {duration_ms} ms outside 0 .. 655350")
+        if loop is not None and not 0 <= int(loop) <= 65535:
+            raise ValueError(f"GPUGifEncoder: loop count {loop} outside 0 .. 65535")
+        order = list(range(res.t)) if order is None else [int(i) for i in order]
+        if not order or any(not 0 <= i < res.t for i in order):
+            raise ValueError(f"GPUGifEncoder: order must name frames 0 .. {res.t - 1}")
+        with torch.cuda.device(res.out.device):
+            counts = [int(c) for c in res.result.cpu().numpy()]          # the small copy: T byte counts
+            if any(not 0 < c <= res.block_stride for c in counts):
+                raise RuntimeError(f"GPUGifEncoder: byte counts {counts} outside (0, {res.block_stride}]")
+            used = sum(counts)
+            st = self._acquire(used)
+            try:
+                parts = [res.out[i * res.block_stride:i * res.block_stride + c] for i, c in enumerate(counts)]
+                packed = parts[0] if len(parts) == 1 else torch.cat(parts)
+                st.tensor[:used].copy_(packed, non_blocking=True)        # exactly the used bytes
+                ev = torch.cuda.Event()
+                ev.record()
+                st.event = ev
+                ev.synchronize()
+                blocks, at = [], 0
+                for c in counts:
+                    b = bytearray(st.array[at:at + c].tobytes())
+                    b[4:6] = struct.pack("<H", delay)                    # the graphic control extension's delay
+                    blocks.append(bytes(b))
+                    at += c
+            finally:
+                self._release(st)
+        head = b"GIF89a" + struct.pack("<HH", res.w, res.h) + b"\x70\x00\x00"
+        if loop is not None:
+            head += b"\x21\xFF\x0BNETSCAPE2.0\x03\x01" + struct.pack("<H", int(loop)) + b"\x00"
+        with self._lock:
+            self.stats["frames"] += res.t
+            self.stats["bytes"] += used
+        return head + b"".join(blocks[i] for i in order) + b"\x3B"
+
+    def encode(self, frames, duration_ms, loop=0, order=None):
+        return self.fetch(self.launch(frames), duration_ms, loop, order)
+
+    def save(self, frames, path, duration_ms, loop=0, order=None):
+        """Encode and write ``path``; returns the byte count."""
+        data = self.encode(frames, duration_ms, loop, order)
+        with open(os.fspath(path), "wb") as fh:
+            fh.write(data)
+        return len(data)

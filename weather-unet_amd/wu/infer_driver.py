@@ -292,16 +292,23 @@ def demo_frames(transfer, batch, pred, thetas, alpha=1.0, **axis_sweep_kw):
     return grid.demo_tables(batch, axis_sweep(transfer, batch, pred, thetas, alpha, **axis_sweep_kw), out="uint8")
 
 
-def save_demo(frames_u8, out, encoder=None, png_encoder=None, ext=".jpg", stem="frame"):
-    """Writes the frames of ``demo_frames``.  ``out`` ending in .gif: the animation of demo.py:86-92, written by Pillow from the fetched
-    bytes -- ping-pong order ``frames[0], frames[1:] + frames[1:-1][::-1]``, ``duration=1000 // T``, ``loop=0`` (palette and LZW stay on
-    the host).  Anything else is a directory: one file ``{stem}{t:04d}{ext}`` per frame through the GPU encoders, routed by ``ext`` as
-    ``save_images`` routes.  Returns the path of the GIF, or the list of files."""
+def save_demo(frames_u8, out, encoder=None, png_encoder=None, ext=".jpg", stem="frame", gif_encoder=None):
+    """Writes the frames of ``demo_frames``.  ``out`` ending in .gif: the animation of demo.py:86-92 -- ping-pong order ``frames[0],
+    frames[1:] + frames[1:-1][::-1]``, ``duration=1000 // T``, ``loop=0``.  With ``gif_encoder`` (a ``wu.gif_enc.GPUGifEncoder``) palette
+    and LZW run on the GPU, every distinct frame once, and the finished image blocks are what is fetched; without it Pillow writes the file
+    from the frames fetched as raw RGB.  Anything else is a directory: one file ``{stem}{t:04d}{ext}`` per frame through the GPU encoders,
+    routed by ``ext`` as ``save_images`` routes.  Returns the path of the GIF, or the list of files."""
     if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
         raise ValueError(f"save_demo: (T, Hg, Wg, 3) uint8 frames, got {tuple(frames_u8.shape)} {frames_u8.dtype}")
     out = os.fspath(out)
     T = frames_u8.shape[0]
     if out.lower().endswith(".gif"):
+        if gif_encoder is not None:
+            from .gif_enc import ping_pong
+            data = gif_encoder.encode(frames_u8, 1000 // T, 0, ping_pong(T))
+            with open(out, "wb") as fh:
+                fh.write(data)
+            return out
         from PIL import Image
         rgb = frames_u8.cpu().numpy()
         imgs = [Image.fromarray(f).convert("RGB") for f in rgb]
