@@ -18,7 +18,7 @@
 // baseline, jccolor's 16.16 fixed point, jcsample's h2v2_downsample with its alternating bias and its asymmetric edge padding,
 // jfdctint's "islow" DCT, quantisation by true integer division, jccoefct's dummy blocks, the Annex K Huffman tables), integer
 // throughout, so the files equal Pillow's byte for byte.
-#include "wu_common.h"
+#include "codec_internal.h"
 
 namespace {
 
@@ -112,27 +112,12 @@ __device__ __forceinline__ Geo make_geo(const JpegEncDesc d, int Hmax, int Wmax,
     return g;
 }
 
-// ---- samples ------------------------------------------------------------------------------------------------------------------
-// the byte wu.infer_driver.to_uint8 makes of a float sample: x * 255 in the tensor's own precision, clamp to [0, 255], truncate
-template <int DT> __device__ __forceinline__ int load_byte(const void* p, long long i);
-template <> __device__ __forceinline__ int load_byte<WU_JPEG_ENC_U8>(const void* p, long long i) { return ((const uint8_t*)p)[i]; }
-__device__ __forceinline__ int float_byte(float x);
-template <> __device__ __forceinline__ int load_byte<WU_F32>(const void* p, long long i) { return float_byte(((const float*)p)[i]); }
-template <> __device__ __forceinline__ int load_byte<WU_BF16>(const void* p, long long i) {
-    const float v = bf16_to_f32(f32_to_bf16(bf16_to_f32(((const bf16_t*)p)[i]) * 255.f));     // the product is rounded to bf16, as torch does
-    return v >= 255.f ? 255 : (v > 0.f ? (int)v : 0);
-}
-
+// ---- samples (float_byte / load_byte<DT>: codec_internal.h) ------------------------------------------------------------------
 // jccolor.c rgb_ycc_convert, FIX(x) = (int)(x * 65536 + 0.5)
 __device__ __forceinline__ int ycc(int r, int g, int b, int comp) {
     if (comp == 0) return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
     if (comp == 1) return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
     return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
-}
-
-__device__ __forceinline__ int float_byte(float x) {
-    const float v = x * 255.f;
-    return v >= 255.f ? 255 : (v > 0.f ? (int)v : 0);             // NaN -> 0
 }
 
 // RGB bytes of the 8 pixels x0 .. x0 + 7 (x0 a multiple of 8) of one row, columns clamped to w - 1.  `vec`: the layout allows wide
@@ -403,20 +388,6 @@ __device__ __forceinline__ unsigned encode_block(const uint4* __restrict__ cp, i
 __device__ __forceinline__ void load_enc_tabs(uint32_t (*sdc)[16], uint32_t (*sac)[256], int tid) {
     for (int i = tid; i < 512; i += 256) sac[i >> 8][i & 255] = kEncTab[2 + (i >> 8)].e[i & 255];
     if (tid < 32) sdc[tid >> 4][tid & 15] = kEncTab[tid >> 4].e[tid & 15];
-}
-
-// inclusive prefix sum over the 256 threads of a workgroup (Hillis-Steele in LDS)
-__device__ __forceinline__ unsigned block_scan_inclusive(unsigned v, unsigned* sm, int tid) {
-    sm[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned add = tid >= off ? sm[tid - off] : 0u;
-        __syncthreads();
-        sm[tid] += add;
-        __syncthreads();
-    }
-    return sm[tid];
 }
 
 // ---- 2. size --------------------------------------------------------------------------------------------------------------------

@@ -165,7 +165,6 @@ __device__ const uint8_t kLenExtra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2,
 __device__ const uint16_t kDistBase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
                                            8193, 12289, 16385, 24577};
 __device__ const uint8_t kDistExtra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-__device__ const uint8_t kClOrderDec[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
 struct CodeTab {               // one Huffman code: canonical decoding data and the first-level table
     uint32_t cnt[16];          // codes per length (cnt[0] = 0)
@@ -400,7 +399,7 @@ __global__ __launch_bounds__(64) void png_dec_inflate_kernel(const uint8_t* __re
         L.len_extra[lane] = lane < 29 ? kLenExtra[lane] : (uint8_t)0;
         L.dist_base[lane] = lane < 30 ? kDistBase[lane] : (uint16_t)0;
         L.dist_extra[lane] = lane < 30 ? kDistExtra[lane] : (uint8_t)0;
-        L.cl_order[lane] = lane < 19 ? kClOrderDec[lane] : (uint8_t)0;
+        L.cl_order[lane] = lane < 19 ? kClOrder[lane] : (uint8_t)0;
     }
     if (lane == 0) {
         L.crc = 0u;

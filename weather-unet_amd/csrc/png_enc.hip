@@ -22,6 +22,7 @@
 // two queues, a leaf winning a tie against an internal node; only the NUMBER of codes per length is taken from the tree (lengths over
 // the limit folded back as zlib's gen_bitlen does), and the lengths go to the symbols in sorted order, longest first.  Literals and
 // end-of-block always give two symbols or more, so the code is complete; the single distance code has length 1 (RFC 1951 3.2.7).
+#include "codec_internal.h"
 #include "png_internal.h"
 
 namespace {
@@ -50,19 +51,6 @@ __host__ __device__ __forceinline__ Geo make_geo(int h, int w, int Hmax, int Wma
     g.len = g.row * g.h;
     g.nseg = (int)((g.len + kSeg - 1) / kSeg);
     return g;
-}
-
-// ---- samples (jpeg_enc.hip's conversion: the byte wu.infer_driver.to_uint8 makes of a float sample) ---------------------------------
-__device__ __forceinline__ int float_byte(float x) {
-    const float v = x * 255.f;
-    return v >= 255.f ? 255 : (v > 0.f ? (int)v : 0);             // NaN -> 0
-}
-template <int DT> __device__ __forceinline__ int load_byte(const void* p, long long i);
-template <> __device__ __forceinline__ int load_byte<WU_PNG_ENC_U8>(const void* p, long long i) { return ((const uint8_t*)p)[i]; }
-template <> __device__ __forceinline__ int load_byte<WU_F32>(const void* p, long long i) { return float_byte(((const float*)p)[i]); }
-template <> __device__ __forceinline__ int load_byte<WU_BF16>(const void* p, long long i) {
-    const float v = bf16_to_f32(f32_to_bf16(bf16_to_f32(((const bf16_t*)p)[i]) * 255.f));     // the product is rounded to bf16, as torch does
-    return v >= 255.f ? 255 : (v > 0.f ? (int)v : 0);
 }
 
 // ---- 1. filter ------------------------------------------------------------------------------------------------------------------------
@@ -231,22 +219,6 @@ struct LsbWriter {             // LSB-first bit stream ORed into zeroed 32-bit L
         if (nacc > 0 && (uint32_t)acc) atomicOr(words + widx, (uint32_t)acc);
     }
 };
-
-// inclusive prefix sum over the 256 threads of a workgroup (Hillis-Steele in LDS)
-__device__ __forceinline__ unsigned block_scan_inclusive(unsigned v, unsigned* sm, int tid) {
-    sm[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned add = tid >= off ? sm[tid - off] : 0u;
-        __syncthreads();
-        sm[tid] += add;
-        __syncthreads();
-    }
-    return sm[tid];
-}
-
-__device__ const uint8_t kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
 // ---- 2. deflate -----------------------------------------------------------------------------------------------------------------------
 // seginfo: 4 words per segment: bytes in the slot, sum of the segment's bytes mod 65521, sum of (len - j) * byte_j mod 65521, 1 = stored

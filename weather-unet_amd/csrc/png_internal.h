@@ -1,5 +1,5 @@
-// What the PNG encoder (png_enc.hip) and decoder (png_dec.hip) share: the segment size of the filtered stream and the CRC-32 by
-// slices -- per-thread CRCs combined by multiplication with x^(8 n) mod P.
+// What the PNG encoder (png_enc.hip) and decoder (png_dec.hip) share: the segment size of the filtered stream, the CRC-32 by
+// slices -- per-thread CRCs combined by multiplication with x^(8 n) mod P -- and deflate's code-length order.
 #pragma once
 #include "wu_common.h"
 
@@ -46,5 +46,8 @@ __device__ __forceinline__ uint32_t crc_shift(uint32_t crc, unsigned after) {
         if (after & 1u) crc = mulmodp(crc, kCrcTab.x8[k]);
     return crc;
 }
+
+// ---- deflate ----------------------------------------------------------------------------------------------------------------------
+__device__ const uint8_t kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};      // RFC 1951 3.2.7: the order of the code-length code's lengths
 
 }  // namespace

@@ -24,8 +24,7 @@ import threading
 
 import torch
 
-from . import _lib
-from .jpeg import _Staging
+from . import _codec, _lib
 from .layout import stream_ptr
 
 
@@ -65,7 +64,7 @@ class GPUGifEncoder:
     bytes into a pinned staging buffer, and assembles the file: header, the blocks in ``order`` with the frame delay written into each,
     trailer.
 
-    Staging-buffer rule (the decoder's): a buffer is refilled only after the event recorded behind the copy that wrote it has completed.
+    Staging buffers: ``wu._codec.StagingPool``.
 
     ``frames``: (T, H, W, 3) uint8 on the GPU, any non-negative strides (what ``wu.grid.demo_tables(..., out="uint8")`` returns).
     """
@@ -73,36 +72,13 @@ class GPUGifEncoder:
         self.device = torch.device(device)
         self.max_staging = int(max_staging)
         self._lock = threading.Lock()
-        self._staging = []
+        self._staging = _codec.StagingPool(self.max_staging)
         self.stats = {"frames": 0, "bytes": 0}
         self._lib = _lib.load()
         self.segment_pixels = int(self._lib.wu_gif_enc_segment_pixels())
 
     def close(self):
-        with self._lock:
-            self._staging.clear()
-
-    # ---- staging buffers (the rule of GPUJpegDecoder._acquire) ----
-    def _acquire(self, nbytes):
-        with self._lock:
-            free = [s for s in self._staging if not s.held]
-            for s in free:
-                if s.tensor.numel() >= nbytes and (s.event is None or s.event.query()):
-                    s.held = True
-                    return s
-            if len(self._staging) >= self.max_staging and free:
-                s = free[0]
-                self._staging.remove(s)
-                if s.event is not None:
-                    s.event.synchronize()
-            s = _Staging(max(int(nbytes * 1.25), 1 << 20), torch.cuda.is_available())
-            s.held = True
-            self._staging.append(s)
-            return s
-
-    def _release(self, s):
-        with self._lock:
-            s.held = False
+        self._staging.clear()
 
     # ---- device stage ----
     def launch(self, frames):
@@ -147,30 +123,15 @@ class GPUGifEncoder:
             counts = [int(c) for c in res.result.cpu().numpy()]          # the small copy: T byte counts
             if any(not 0 < c <= res.block_stride for c in counts):
                 raise RuntimeError(f"GPUGifEncoder: byte counts {counts} outside (0, {res.block_stride}]")
-            used = sum(counts)
-            st = self._acquire(used)
-            try:
-                parts = [res.out[i * res.block_stride:i * res.block_stride + c] for i, c in enumerate(counts)]
-                packed = parts[0] if len(parts) == 1 else torch.cat(parts)
-                st.tensor[:used].copy_(packed, non_blocking=True)        # exactly the used bytes
-                ev = torch.cuda.Event()
-                ev.record()
-                st.event = ev
-                ev.synchronize()
-                blocks, at = [], 0
-                for c in counts:
-                    b = bytearray(st.array[at:at + c].tobytes())
-                    b[4:6] = struct.pack("<H", delay)                    # the graphic control extension's delay
-                    blocks.append(bytes(b))
-                    at += c
-            finally:
-                self._release(st)
+            blocks = _codec.fetch_packed(self._staging, res.out, res.block_stride, counts)
+        for i, b in enumerate(blocks):
+            blocks[i] = b[:4] + struct.pack("<H", delay) + b[6:]         # the graphic control extension's delay
         head = b"GIF89a" + struct.pack("<HH", res.w, res.h) + b"\x70\x00\x00"
         if loop is not None:
             head += b"\x21\xFF\x0BNETSCAPE2.0\x03\x01" + struct.pack("<H", int(loop)) + b"\x00"
         with self._lock:
             self.stats["frames"] += res.t
-            self.stats["bytes"] += used
+            self.stats["bytes"] += sum(counts)
         return head + b"".join(blocks[i] for i in order) + b"\x3B"
 
     def encode(self, frames, duration_ms, loop=0, order=None):

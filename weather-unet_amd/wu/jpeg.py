@@ -14,22 +14,20 @@ same worker thread, counted in ``stats`` and copied into its slot: the batch is 
 ``parse`` and ``entropy_decode`` are host-only and work without a GPU.
 """
 import ctypes
-import io
-import os
 import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _codec, _lib
+from ._codec import MAX_THREADS  # noqa: F401 -- a public name of this module
 from .layout import stream_ptr
 
 MODE_GREY, MODE_444, MODE_H2V1, MODE_H2V2 = 0, 1, 2, 3
 REASONS = {0: "ok", 1: "not-jpeg", 2: "corrupt-header", 3: "progressive", 4: "arithmetic", 5: "precision", 6: "lossless",
            7: "colorspace", 8: "qtable16", 9: "sampling", 10: "multiscan", 11: "magnitude"}
 TILE_BLOCKS = 32          # blocks per IDCT workgroup (csrc/jpeg.hip kTileBlocks)
-MAX_THREADS = 16
 MAX_NATIVE_PIXELS = 89478485          # Pillow's Image.MAX_IMAGE_PIXELS default: larger images go through Pillow (which warns or refuses)
 
 
@@ -63,19 +61,6 @@ class JpegError(ValueError):
     """Corrupt entropy-coded data (bad Huffman code, bad restart sequence, premature end ...)."""
 
 
-def _read(item):
-    if isinstance(item, (bytes, bytearray, memoryview)):
-        return bytes(item)
-    with open(os.fspath(item), "rb") as fh:
-        return fh.read()
-
-
-def _name(item, i=None):
-    if isinstance(item, (bytes, bytearray, memoryview)):
-        return f"<bytes #{i}>" if i is not None else "<bytes>"
-    return os.fspath(item)
-
-
 def _parse_bytes(lib, data):
     info = JpegInfo()
     _lib.check(lib.wu_jpeg_parse(data, len(data), ctypes.byref(info)), "wu_jpeg_parse")
@@ -87,7 +72,7 @@ def parse(data):
     Host only."""
     lib = _lib.load()
     assert lib.wu_jpeg_info_bytes() == ctypes.sizeof(JpegInfo)
-    return _parse_bytes(lib, _read(data))
+    return _parse_bytes(lib, _codec.read(data))
 
 
 def _entropy_into(lib, data, info, coef_ptr, capacity, qtab_ptr):
@@ -103,7 +88,7 @@ def entropy_decode(data):
     """Host stage alone (tests, tools): returns (planes, qtabs, info) with planes[c] a (blocks_h, blocks_w, 64) int16 array of
     QUANTISED coefficients in natural order and qtabs a (3, 64) uint16 array in natural order.  Raises JpegUnsupported / JpegError."""
     lib = _lib.load()
-    data = _read(data)
+    data = _codec.read(data)
     info = _parse_bytes(lib, data)
     if not info.supported:
         raise JpegUnsupported(info.reason_name)
@@ -119,53 +104,18 @@ def entropy_decode(data):
     return planes, qtabs, info
 
 
-def _pillow_rgb(data, name):
-    from PIL import Image
-    try:
-        return np.array(Image.open(io.BytesIO(data)).convert("RGB"), dtype=np.uint8)          # a writable, contiguous copy
-    except Exception as e:                                              # noqa: BLE001 -- whatever Pillow raises, name the file
-        raise RuntimeError(f"cannot decode image {name}: {type(e).__name__}: {e}") from e
-
-
-def _align(v, a=256):
-    return (v + a - 1) // a * a
-
-
-class _Staging:
-    """One host staging buffer (pinned when a GPU is present) and the event recorded after the last copy that read it."""
-    def __init__(self, nbytes, pinned):
-        self.tensor = torch.empty(nbytes, dtype=torch.uint8, pin_memory=pinned)
-        self.array = self.tensor.numpy()
-        self.ptr = self.tensor.data_ptr()
-        self.event = None         # torch.cuda.Event of the last H2D copy out of this buffer
-        self.held = False         # a HostBatch owns it
-
-
-class HostBatch:
+class HostBatch(_codec.HostBatch):
     """Result of GPUJpegDecoder.prepare: entropy-decoded coefficients and descriptors of one batch in a staging buffer.  It owns
     the buffer until it is released (``release()`` or garbage collection), so it may be finished more than once."""
-    def __init__(self, decoder):
-        self._decoder = decoder
-        self.staging = None
+    def __init__(self, pool):
+        super().__init__(pool)
         self.n = 0
         self.sizes = []
         self.hmax = self.wmax = 0
         self.n_tiles = 0
-        self.used = 0
         self.off = {}
         self.fallbacks = []       # (slot, (h, w, 3) uint8 array) decoded by Pillow
         self.names = []
-
-    def release(self):
-        if self.staging is not None:
-            self._decoder._release(self.staging)
-            self.staging = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:         # noqa: BLE001 -- interpreter shutdown
-            pass
 
 
 class DeviceBatch:
@@ -183,19 +133,18 @@ class GPUJpegDecoder:
     host-to-device copy of the used part of that buffer and the two reconstruction launches on the CURRENT stream, and belongs to
     the thread that owns the stream.
 
-    Staging-buffer rule: a buffer may be refilled only after the copy that read it has completed.  Every buffer carries an event
-    recorded right after its copy; ``prepare`` takes a buffer only if no HostBatch holds it and its event has completed (checked
-    with ``query()`` on the host, never waited for on the GPU), and allocates another one otherwise.  Past ``max_staging`` buffers
-    it blocks the HOST on the oldest event instead of growing further.
+    Staging-buffer rule (``wu._codec.StagingPool``): a buffer may be refilled only after the copy that read it has completed.
+    Every buffer carries an event recorded right after its copy; ``prepare`` takes a buffer only if no HostBatch holds it and its
+    event has completed (checked with ``query()`` on the host, never waited for on the GPU), and allocates another one otherwise.
+    Past ``max_staging`` buffers it blocks the HOST on the oldest event instead of growing further.
     """
     def __init__(self, device="cuda", threads=None, max_staging=8):
-        n = min(MAX_THREADS, os.cpu_count() or 1) if threads is None else int(threads)
-        self.threads = max(1, min(MAX_THREADS, n))
+        self.threads = _codec.worker_threads(threads)
         self.device = torch.device(device)
         self.max_staging = int(max_staging)
         self._pool = ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="wu-jpeg")
         self._lock = threading.Lock()
-        self._staging = []
+        self._staging = _codec.StagingPool(self.max_staging)
         self.stats = {"native": 0, "fallback": 0, "fallback_reasons": {}}
         self._lib = _lib.load()
         assert self._lib.wu_jpeg_info_bytes() == ctypes.sizeof(JpegInfo) and self._lib.wu_jpeg_desc_bytes() == 64
@@ -203,45 +152,15 @@ class GPUJpegDecoder:
     def close(self):
         self._pool.shutdown(wait=True)
 
-    # ---- staging buffers ----
-    def _acquire(self, nbytes):
-        with self._lock:
-            free = [s for s in self._staging if not s.held]
-            for s in free:
-                if s.tensor.numel() >= nbytes and (s.event is None or s.event.query()):
-                    s.held = True
-                    return s
-            if len(self._staging) >= self.max_staging and free:
-                s = free[0]                                            # full house: wait on the HOST for the oldest copy
-                self._staging.remove(s)
-                if s.event is not None:
-                    s.event.synchronize()
-            s = _Staging(max(int(nbytes * 1.25), 1 << 20), torch.cuda.is_available())
-            s.held = True
-            self._staging.append(s)
-            return s
-
-    def _release(self, s):
-        with self._lock:
-            s.held = False
-
-    def _count(self, reason):
-        with self._lock:
-            if reason is None:
-                self.stats["native"] += 1
-            else:
-                self.stats["fallback"] += 1
-                self.stats["fallback_reasons"][reason] = self.stats["fallback_reasons"].get(reason, 0) + 1
-
     # ---- host stage ----
     def _open(self, arg):
         i, item = arg
-        data = _read(item)
+        data = _codec.read(item)
         info = _parse_bytes(self._lib, data)
         if info.supported and info.height * info.width <= MAX_NATIVE_PIXELS:
             return data, info, None, None
         # a header may claim any size up to 65535 x 65535: beyond Pillow's own decompression-bomb threshold the file is Pillow's to judge
-        return data, info, _pillow_rgb(data, _name(item, i)), (info.reason_name if not info.supported else "too-large")
+        return data, info, _codec.pillow_rgb(data, _codec.name(item, i)), (info.reason_name if not info.supported else "too-large")
 
     def prepare(self, items):
         """Read + parse + entropy-decode ``items`` (bytes objects or paths) into a staging buffer; returns a HostBatch."""
@@ -249,21 +168,21 @@ class GPUJpegDecoder:
         if not items:
             raise ValueError("GPUJpegDecoder: empty batch")
         opened = list(self._pool.map(self._open, enumerate(items)))
-        hb = HostBatch(self)
+        hb = HostBatch(self._staging)
         hb.n = n = len(items)
-        hb.names = [_name(it, i) for i, it in enumerate(items)]
+        hb.names = [_codec.name(it, i) for i, it in enumerate(items)]
         first_block, first_tile, tiles = [0] * n, [0] * n, 0
         for i, (_, info, rgb, _) in enumerate(opened):
             first_tile[i], first_block[i] = tiles, tiles * TILE_BLOCKS
             if rgb is None:
                 tiles += (info.total_blocks + TILE_BLOCKS - 1) // TILE_BLOCKS
         off = {"coef": 0}
-        off["qtab"] = _align(tiles * TILE_BLOCKS * 128)
-        off["desc"] = _align(off["qtab"] + n * 384)
-        off["tile"] = _align(off["desc"] + n * 64)
-        hb.used = _align(off["tile"] + max(tiles, 1) * 4)
+        off["qtab"] = _codec.align(tiles * TILE_BLOCKS * 128)
+        off["desc"] = _codec.align(off["qtab"] + n * 384)
+        off["tile"] = _codec.align(off["desc"] + n * 64)
+        hb.used = _codec.align(off["tile"] + max(tiles, 1) * 4)
         hb.off, hb.n_tiles = off, tiles
-        st = hb.staging = self._acquire(hb.used)
+        st = hb.staging = self._staging.acquire(hb.used)
         desc = st.array[off["desc"]:off["desc"] + n * 64].view(np.int32).reshape(n, 16)
         tile = st.array[off["tile"]:off["tile"] + max(tiles, 1) * 4].view(np.int32)
         desc[:] = 0
@@ -277,14 +196,14 @@ class GPUJpegDecoder:
             try:
                 rc = _entropy_into(self._lib, data, info, st.ptr + first_block[i] * 128, cap, st.ptr + off["qtab"] + i * 384)
             except JpegError:
-                return _pillow_rgb(data, hb.names[i]), "corrupt-scan"      # Pillow is the arbiter; it raises on a truncated file
+                return _codec.pillow_rgb(data, hb.names[i]), "corrupt-scan"      # Pillow is the arbiter; it raises on a truncated file
             if rc == 1:
-                return _pillow_rgb(data, hb.names[i]), "magnitude"
+                return _codec.pillow_rgb(data, hb.names[i]), "magnitude"
             return None, None
 
         results = list(self._pool.map(decode, range(n)))
         for i, ((_, info, _, _), (rgb, reason)) in enumerate(zip(opened, results)):
-            self._count(reason)
+            _codec.count(self.stats, self._lock, reason)
             if rgb is not None:
                 hb.fallbacks.append((i, rgb))
                 hb.sizes.append((int(rgb.shape[0]), int(rgb.shape[1])))
@@ -305,14 +224,8 @@ class GPUJpegDecoder:
         if not torch.cuda.is_available() or self.device.type != "cuda":
             raise RuntimeError("GPUJpegDecoder: the reconstruction runs HIP kernels on an MI355X only -- there is no CPU fallback "
                                "(wu.jpeg.parse / entropy_decode are the host-only entry points)")
-        if hb.staging is None:
-            raise RuntimeError("GPUJpegDecoder: this HostBatch was released")
         with torch.cuda.device(self.device):                          # the copy and its event go to this device's current stream
-            buf = torch.empty(hb.used, dtype=torch.uint8, device=self.device)
-            buf.copy_(hb.staging.tensor[:hb.used], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            hb.staging.event = ev
+            buf = _codec.upload(hb, self.device, "GPUJpegDecoder")
             ws = torch.empty(max(int(self._lib.wu_jpeg_workspace_bytes(hb.n_tiles * TILE_BLOCKS)), 256), dtype=torch.uint8, device=self.device)
         return DeviceBatch(buf, hb.off, ws, hb.n, hb.hmax, hb.wmax, hb.n_tiles)
 

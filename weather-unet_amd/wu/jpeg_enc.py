@@ -18,21 +18,17 @@ counted in ``stats``, exactly as the decoder counts its fallbacks.
 """
 import ctypes
 import io
-import os
 import threading
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from . import _lib
-from .jpeg import _Staging
+from . import _codec, _lib
+from ._codec import MAX_THREADS, U8  # noqa: F401 -- public names of this module; U8 is WU_JPEG_ENC_U8
 from .layout import stream_ptr
 
 SUBSAMPLING = {"4:2:0": 0, "4:4:4": 1}       # WU_JPEG_ENC_420 / WU_JPEG_ENC_444
 _PILLOW_SUBSAMPLING = {"4:2:0": 2, "4:4:4": 0}
-U8 = 2                                       # WU_JPEG_ENC_U8
-MAX_THREADS = 16
 MIN_CAPACITY = 1024                          # bytes; a few-pixel image may well take more than its raw size
 
 
@@ -89,7 +85,7 @@ class DeviceResult:
         self.n, self.out_stride = plan.n, plan.out_stride
 
 
-class GPUJpegEncoder:
+class GPUJpegEncoder(_codec.BatchFileEncoder):
     """Batch JPEG encoder on the GPU with Pillow's bytes.
 
     ``encode_batch(images, sizes)`` = ``fetch(launch(images, sizes))``.  ``launch`` runs the five kernels on the CURRENT stream and
@@ -97,97 +93,37 @@ class GPUJpegEncoder:
     run outside the capture (that first launch uploads the descriptors and headers).  ``fetch`` does one small device-to-host copy
     of the N byte counts and flags, then one copy of exactly the used bytes into a pinned staging buffer.
 
-    Staging-buffer rule (the decoder's): a buffer is refilled only after the event recorded behind the copy that wrote it has
-    completed.
+    ``save_batch`` / ``save_batch_async`` / ``close``: ``wu._codec.BatchFileEncoder``.  Staging buffers: ``wu._codec.StagingPool``.
 
     ``images``: (N, H, W, 3) uint8, or (N, 3, H, W) float32 / bfloat16 with samples in [0, 1] (any strides: contiguous, channels-last,
     a slice ...), converted as ``wu.infer_driver.to_uint8`` does.  ``sizes``: [(h, w)] per image for a padded batch (what
     ``GPUJpegDecoder`` emits); the padding is never read.
     """
     def __init__(self, device="cuda", quality=75, subsampling="4:2:0", threads=None, max_staging=8):
-        n = min(MAX_THREADS, os.cpu_count() or 1) if threads is None else int(threads)
-        self.threads = max(1, min(MAX_THREADS, n))
         self.device = torch.device(device)
         self.quality = int(quality)
         if not 1 <= self.quality <= 100:
             raise ValueError(f"GPUJpegEncoder: quality {quality} outside 1..100")
         self.subsampling = _subsampling(subsampling)
         self.max_staging = int(max_staging)
-        self._pool = ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="wu-jpeg-enc")
-        self._lock = threading.Lock()
-        self._staging = []
-        self._plans = {}
+        self._start_pool(threads, "wu-jpeg-enc", "GPUJpegEncoder")
+        self._lock = threading.Lock()         # guards stats
+        self._staging = _codec.StagingPool(self.max_staging)
+        self._plans = _codec.PlanCache("GPUJpegEncoder", "the descriptors and headers")
         self._qtab = None
-        self._io = self._side = None          # background writer of save_batch_async: one thread, one side stream, made on first use
         self.stats = {"native": 0, "fallback": 0, "fallback_reasons": {}}
         self._lib = _lib.load()
         assert self._lib.wu_jpeg_enc_desc_bytes() == 16
         self.header_bytes = int(self._lib.wu_jpeg_enc_header_bytes())
 
-    def close(self):
-        if self._io is not None:
-            self._io.shutdown(wait=True)
-        self._pool.shutdown(wait=True)
-
     def header(self, h, w):
         return header(h, w, self.quality, self.subsampling)
 
-    # ---- staging buffers (the rule of GPUJpegDecoder._acquire) ----
-    def _acquire(self, nbytes):
-        with self._lock:
-            free = [s for s in self._staging if not s.held]
-            for s in free:
-                if s.tensor.numel() >= nbytes and (s.event is None or s.event.query()):
-                    s.held = True
-                    return s
-            if len(self._staging) >= self.max_staging and free:
-                s = free[0]
-                self._staging.remove(s)
-                if s.event is not None:
-                    s.event.synchronize()
-            s = _Staging(max(int(nbytes * 1.25), 1 << 20), torch.cuda.is_available())
-            s.held = True
-            self._staging.append(s)
-            return s
-
-    def _release(self, s):
-        with self._lock:
-            s.held = False
-
-    def _count(self, reason):
-        with self._lock:
-            if reason is None:
-                self.stats["native"] += 1
-            else:
-                self.stats["fallback"] += 1
-                self.stats["fallback_reasons"][reason] = self.stats["fallback_reasons"].get(reason, 0) + 1
-
     # ---- device stage ----
-    @staticmethod
-    def _geometry(images):
-        """(dtype code, N, H, W, element strides (n, c, y, x))."""
-        if not isinstance(images, torch.Tensor) or images.dim() != 4:
-            raise ValueError("GPUJpegEncoder: images must be a 4-d tensor, (N,H,W,3) uint8 or (N,3,H,W) float32 / bfloat16")
-        if images.dtype == torch.uint8:
-            if images.shape[3] != 3:
-                raise ValueError(f"GPUJpegEncoder: a uint8 batch is (N,H,W,3), got {tuple(images.shape)}")
-            sn, sy, sx, sc = images.stride()
-            return U8, images.shape[0], images.shape[1], images.shape[2], (sn, sc, sy, sx)
-        if images.dtype in (torch.float32, torch.bfloat16):
-            if images.shape[1] != 3:
-                raise ValueError(f"GPUJpegEncoder: a float batch is (N,3,H,W), got {tuple(images.shape)}")
-            sn, sc, sy, sx = images.stride()
-            return (_lib.F32 if images.dtype == torch.float32 else _lib.BF16), images.shape[0], images.shape[2], images.shape[3], (sn, sc, sy, sx)
-        raise ValueError(f"GPUJpegEncoder: dtype {images.dtype} is not uint8 / float32 / bfloat16")
-
     def _plan(self, n, hmax, wmax, sizes, capacity):
-        key = (n, hmax, wmax, tuple(sizes), capacity)
-        plan = self._plans.get(key)
-        if plan is not None:
-            return plan
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("GPUJpegEncoder.launch: this batch geometry has not been launched yet -- run launch once outside the "
-                               "capture (it uploads the descriptors and headers), then capture")
+        return self._plans.get((n, hmax, wmax, tuple(sizes), capacity), lambda: self._make_plan(n, hmax, wmax, sizes, capacity))
+
+    def _make_plan(self, n, hmax, wmax, sizes, capacity):
         caps = [max(h * w * 3, MIN_CAPACITY) if capacity is None else int(capacity) for h, w in sizes]
         cap_max = max(caps)
         sub = SUBSAMPLING[self.subsampling]
@@ -203,29 +139,17 @@ class GPUJpegEncoder:
             hdr[i, :self.header_bytes] = np.frombuffer(self.header(h, w), dtype=np.uint8)
         if self._qtab is None:
             self._qtab = torch.from_numpy(quant_tables(self.quality).view(np.int16)).to(self.device)
-        plan = _Plan(torch.from_numpy(desc).to(self.device), torch.from_numpy(hdr).to(self.device), hdr_stride, ws_bytes, out_stride,
+        return _Plan(torch.from_numpy(desc).to(self.device), torch.from_numpy(hdr).to(self.device), hdr_stride, ws_bytes, out_stride,
                      cap_max, n, hmax, wmax)
-        if len(self._plans) >= 64:                                    # a stream of ever-changing geometries must not grow without bound
-            self._plans.pop(next(iter(self._plans)))
-        self._plans[key] = plan
-        return plan
 
     def launch(self, images, sizes=None, capacity=None):
         """The five kernels on the current stream; returns a DeviceResult.  ``capacity``: bytes of entropy-coded data each image may
         take (default: its raw size h * w * 3, at least 1 KiB)."""
-        dt, n, hmax, wmax, strides = self._geometry(images)
+        dt, n, hmax, wmax, strides = _codec.batch_geometry(images, "GPUJpegEncoder")
         if not images.is_cuda or not torch.cuda.is_available() or self.device.type != "cuda":
             raise RuntimeError("GPUJpegEncoder: the encoder runs HIP kernels on an MI355X only -- there is no CPU fallback "
                                "(wu.jpeg_enc.header / quant_tables are the host-only entry points)")
-        if n < 1 or hmax < 1 or wmax < 1:
-            raise ValueError("GPUJpegEncoder: empty batch")
-        if sizes is None:
-            sizes = [(hmax, wmax)] * n
-        sizes = [(int(h), int(w)) for h, w in sizes]
-        if len(sizes) != n or any(not (1 <= h <= hmax and 1 <= w <= wmax) for h, w in sizes):
-            raise ValueError(f"GPUJpegEncoder: sizes must be {n} pairs (h, w) inside the batch's {hmax} x {wmax}")
-        if any(s < 0 for s in strides):
-            raise ValueError("GPUJpegEncoder: negative strides")
+        sizes = _codec.check_sizes(n, hmax, wmax, sizes, strides, "GPUJpegEncoder")
         with torch.cuda.device(images.device):
             plan = self._plan(n, hmax, wmax, sizes, None if capacity is None else int(capacity))
             ws = torch.empty(plan.ws_bytes, dtype=torch.uint8, device=images.device)
@@ -253,71 +177,14 @@ class GPUJpegEncoder:
             native = [i for i in range(res.n) if not info[i, 1]]
             pending = {i: self._fallback(res, i) for i in range(res.n) if info[i, 1]}
             files = [None] * res.n
-            if native:
-                used = int(sum(int(info[i, 0]) for i in native))
-                st = self._acquire(used)
-                try:
-                    parts = [res.out[i * res.out_stride:i * res.out_stride + int(info[i, 0])] for i in native]
-                    packed = parts[0] if len(parts) == 1 else torch.cat(parts)
-                    st.tensor[:used].copy_(packed, non_blocking=True)    # exactly the used bytes
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    st.event = ev
-                    ev.synchronize()
-                    at = 0
-                    for i in native:
-                        files[i] = st.array[at:at + int(info[i, 0])].tobytes()
-                        at += int(info[i, 0])
-                finally:
-                    self._release(st)
+            counts = [int(c) for c in info[:, 0]]
+            for i, f in zip(native, _codec.fetch_packed(self._staging, res.out, res.out_stride, counts, native)):
+                files[i] = f
         for i in range(res.n):
-            self._count("capacity" if i in pending else None)
+            _codec.count(self.stats, self._lock, "capacity" if i in pending else None)
             if i in pending:
                 files[i] = pending[i].result()
         return files
 
     def encode_batch(self, images, sizes=None, capacity=None):
         return self.fetch(self.launch(images, sizes, capacity))
-
-    def save_batch(self, images, paths, sizes=None):
-        """Encode and write ``paths[i]``; returns the byte counts."""
-        paths = self._check_paths(images, paths)
-        files = self.encode_batch(images, sizes)
-        list(self._pool.map(_write, zip(paths, files)))
-        return [len(f) for f in files]
-
-    def save_batch_async(self, images, paths, sizes=None):
-        """``save_batch`` without waiting: the kernels are launched on the current stream now, the copies to the host and the file
-        writes happen on a background thread (on a side stream, behind an event recorded after the kernels), so the caller can
-        queue the next forward at once.  Returns a Future of the byte counts; batches complete in the order they were submitted.
-        The caller must not overwrite ``images`` before the Future is done."""
-        paths = self._check_paths(images, paths)
-        res = self.launch(images, sizes)
-        with torch.cuda.device(res.out.device):
-            ev = torch.cuda.Event()
-            ev.record()
-        with self._lock:
-            if self._io is None:
-                self._io = ThreadPoolExecutor(max_workers=1, thread_name_prefix="wu-jpeg-enc-io")
-                self._side = torch.cuda.Stream(device=res.out.device)
-        return self._io.submit(self._finish_save, res, ev, paths)
-
-    def _finish_save(self, res, ev, paths):
-        with torch.cuda.device(res.out.device), torch.cuda.stream(self._side):
-            self._side.wait_event(ev)
-            files = self.fetch(res)
-        list(self._pool.map(_write, zip(paths, files)))
-        return [len(f) for f in files]
-
-    @staticmethod
-    def _check_paths(images, paths):
-        paths = [os.fspath(p) for p in paths]
-        if len(paths) != images.shape[0]:
-            raise ValueError(f"GPUJpegEncoder: {len(paths)} paths for {images.shape[0]} images")
-        return paths
-
-
-def _write(arg):
-    path, data = arg
-    with open(path, "wb") as fh:
-        fh.write(data)

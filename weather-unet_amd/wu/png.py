@@ -20,15 +20,14 @@ kernels ran, so the N status words are copied back and waited for before the rej
 ``parse`` is host-only and works without a GPU; so do ``prepare`` and ``buffer_sizes``.
 """
 import ctypes
-import os
 import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from . import _lib
-from .jpeg import MAX_NATIVE_PIXELS, MAX_THREADS, _Staging, _align, _name, _pillow_rgb, _read
+from . import _codec, _lib
+from .jpeg import MAX_NATIVE_PIXELS
 from .layout import stream_ptr
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
@@ -71,20 +70,18 @@ def parse(data, max_pixels=MAX_NATIVE_PIXELS):
     Host only."""
     lib = _lib.load()
     assert lib.wu_png_dec_info_bytes() == ctypes.sizeof(PngInfo)
-    return _parse_bytes(lib, _read(data), max_pixels)
+    return _parse_bytes(lib, _codec.read(data), max_pixels)
 
 
-class HostBatch:
+class HostBatch(_codec.HostBatch):
     """Result of GPUPngDecoder.prepare: the files of one batch, their descriptors and the segment table in a staging buffer.  It owns
     the buffer until it is released (``release()`` or garbage collection), so it may be finished more than once."""
-    def __init__(self, decoder):
-        self._decoder = decoder
-        self.staging = None
+    def __init__(self, pool):
+        super().__init__(pool)
         self.n = 0
         self.sizes = []
         self.hmax = self.wmax = 0
         self.n_segments = 0
-        self.used = 0
         self.off = {}
         self.file_off = []        # per image: offset of its bytes in the staging buffer (None: decoded by Pillow in prepare)
         self.file_len = []
@@ -93,17 +90,6 @@ class HostBatch:
         self.names = []
         self.counted = False      # its images are in the decoder's stats
         self.last_status = None   # device status per image of the last finish
-
-    def release(self):
-        if self.staging is not None:
-            self._decoder._release(self.staging)
-            self.staging = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:         # noqa: BLE001 -- interpreter shutdown
-            pass
 
 
 class GPUPngDecoder:
@@ -115,19 +101,17 @@ class GPUPngDecoder:
     launches on the CURRENT stream, then copies the N status words back and waits for them -- one host synchronisation per batch --
     and decodes the images the device rejected with Pillow into their zeroed slots.
 
-    Staging-buffer rule (``GPUJpegDecoder``'s): a buffer is refilled only after the event recorded behind the copy that read it has
-    completed.
+    Staging buffers: ``wu._codec.StagingPool``.
 
     ``stats``: images decoded natively, images decoded by Pillow, and the latter by reason (a parser reason or a device status).
     """
     def __init__(self, device="cuda", threads=None, max_staging=8):
-        n = min(MAX_THREADS, os.cpu_count() or 1) if threads is None else int(threads)
-        self.threads = max(1, min(MAX_THREADS, n))
+        self.threads = _codec.worker_threads(threads)
         self.device = torch.device(device)
         self.max_staging = int(max_staging)
         self._pool = ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="wu-png")
         self._lock = threading.Lock()
-        self._staging = []
+        self._staging = _codec.StagingPool(self.max_staging)
         self.stats = {"native": 0, "fallback": 0, "fallback_reasons": {}}
         self._lib = _lib.load()
         assert (self._lib.wu_png_dec_info_bytes() == ctypes.sizeof(PngInfo) and self._lib.wu_png_dec_desc_bytes() == DESC_BYTES
@@ -136,44 +120,14 @@ class GPUPngDecoder:
     def close(self):
         self._pool.shutdown(wait=True)
 
-    # ---- staging buffers (the rule of GPUJpegDecoder._acquire) ----
-    def _acquire(self, nbytes):
-        with self._lock:
-            free = [s for s in self._staging if not s.held]
-            for s in free:
-                if s.tensor.numel() >= nbytes and (s.event is None or s.event.query()):
-                    s.held = True
-                    return s
-            if len(self._staging) >= self.max_staging and free:
-                s = free[0]                                            # full house: wait on the HOST for the oldest copy
-                self._staging.remove(s)
-                if s.event is not None:
-                    s.event.synchronize()
-            s = _Staging(max(int(nbytes * 1.25), 1 << 20), torch.cuda.is_available())
-            s.held = True
-            self._staging.append(s)
-            return s
-
-    def _release(self, s):
-        with self._lock:
-            s.held = False
-
-    def _count(self, reason):
-        with self._lock:
-            if reason is None:
-                self.stats["native"] += 1
-            else:
-                self.stats["fallback"] += 1
-                self.stats["fallback_reasons"][reason] = self.stats["fallback_reasons"].get(reason, 0) + 1
-
     # ---- host stage ----
     def _open(self, arg):
         i, item = arg
-        data = _read(item)
+        data = _codec.read(item)
         info, idat = _parse_bytes(self._lib, data)
         if info.supported and len(data) < 1 << 31:                     # the descriptors hold 32-bit offsets inside a file
             return data, info, idat, None, None
-        return data, info, idat, _pillow_rgb(data, _name(item, i)), (info.reason_name if not info.supported else "too-large")
+        return data, info, idat, _codec.pillow_rgb(data, _codec.name(item, i)), (info.reason_name if not info.supported else "too-large")
 
     def prepare(self, items):
         """Read + parse ``items`` (bytes objects or paths) and stage the native files; returns a HostBatch.  Needs no GPU."""
@@ -181,9 +135,9 @@ class GPUPngDecoder:
         if not items:
             raise ValueError("GPUPngDecoder: empty batch")
         opened = list(self._pool.map(self._open, enumerate(items)))
-        hb = HostBatch(self)
+        hb = HostBatch(self._staging)
         hb.n = n = len(items)
-        hb.names = [_name(it, i) for i, it in enumerate(items)]
+        hb.names = [_codec.name(it, i) for i, it in enumerate(items)]
         at, segs = 0, 0
         first_seg = [0] * n
         for i, (data, info, idat, rgb, reason) in enumerate(opened):
@@ -193,21 +147,21 @@ class GPUPngDecoder:
                 hb.file_len.append(len(data))
                 hb.datas.append(data)
                 hb.sizes.append((info.height, info.width))
-                at = _align(at + len(data), 16)
+                at = _codec.align(at + len(data), 16)
                 segs += info.n_segments
             else:
-                self._count(reason)
+                _codec.count(self.stats, self._lock, reason)
                 hb.file_off.append(None)
                 hb.file_len.append(0)
                 hb.datas.append(None)
                 hb.fallbacks.append((i, rgb))
                 hb.sizes.append((int(rgb.shape[0]), int(rgb.shape[1])))
         off = {"files": 0}
-        off["desc"] = _align(at)
-        off["seg"] = _align(off["desc"] + n * DESC_BYTES)
-        hb.used = _align(off["seg"] + max(segs, 1) * SEG_BYTES)
+        off["desc"] = _codec.align(at)
+        off["seg"] = _codec.align(off["desc"] + n * DESC_BYTES)
+        hb.used = _codec.align(off["seg"] + max(segs, 1) * SEG_BYTES)
         hb.off, hb.n_segments = off, segs
-        st = hb.staging = self._acquire(hb.used)
+        st = hb.staging = self._staging.acquire(hb.used)
         desc = st.array[off["desc"]:off["desc"] + n * DESC_BYTES].view(DESC_DTYPE)
         seg = st.array[off["seg"]:off["seg"] + max(segs, 1) * SEG_BYTES].view(SEG_DTYPE)
         desc[:] = 0
@@ -245,16 +199,12 @@ class GPUPngDecoder:
         if not torch.cuda.is_available() or self.device.type != "cuda":
             raise RuntimeError("GPUPngDecoder: inflate and unfilter run HIP kernels on an MI355X only -- there is no CPU fallback "
                                "(wu.png.parse is the host-only entry point)")
-        if hb.staging is None:
+        if hb.staging is None:                                        # before anything else about the batch is judged
             raise RuntimeError("GPUPngDecoder: this HostBatch was released")
         sizes = self.buffer_sizes(hb)
         ws_bytes = sizes["workspace"]
         with torch.cuda.device(self.device):                          # the copy and its event go to this device's current stream
-            buf = torch.empty(hb.used, dtype=torch.uint8, device=self.device)
-            buf.copy_(hb.staging.tensor[:hb.used], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            hb.staging.event = ev
+            buf = _codec.upload(hb, self.device, "GPUPngDecoder")
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
             out = torch.empty((hb.n, hb.hmax, hb.wmax, 3), dtype=torch.uint8, device=self.device)
             status = torch.empty(hb.n, dtype=torch.int32, device=self.device)
@@ -269,14 +219,14 @@ class GPUPngDecoder:
                     continue
                 if code == 0:
                     if not hb.counted:
-                        self._count(None)
+                        _codec.count(self.stats, self._lock, None)
                     continue
-                rgb = _pillow_rgb(hb.datas[i], hb.names[i])
+                rgb = _codec.pillow_rgb(hb.datas[i], hb.names[i])
                 if rgb.shape[:2] != hb.sizes[i]:
                     raise RuntimeError(f"cannot decode image {hb.names[i]}: Pillow reads {rgb.shape[1]} x {rgb.shape[0]}, the header "
                                        f"says {hb.sizes[i][1]} x {hb.sizes[i][0]}")
                 if not hb.counted:
-                    self._count(STATUS.get(int(code), str(int(code))))
+                    _codec.count(self.stats, self._lock, STATUS.get(int(code), str(int(code))))
                 late.append((i, rgb))
             hb.counted = True
             for slot, rgb in hb.fallbacks + late:                      # the second, small H2D path: the kernels zeroed these slots
