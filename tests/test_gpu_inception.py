@@ -1,6 +1,8 @@
 """InceptionV3 / FID on the GPU (csrc/inception.hip, wu/inception.py, wu/fid.py) against the float64 CPU restatement
 tests/_inception_ref.py (torch.nn.functional ops, written from the architecture; torchvision is not importable here).
-bf16 cases compare against float64 results of bf16-rounded operands where a single kernel is tested."""
+bf16 cases compare against float64 results of bf16-rounded operands where a single kernel is tested.
+Everything here runs at the shapes of a square 299 x 299 network input; tests/test_gpu_inception_edges.py covers H != W, channel slices,
+the batch split, small pool maps, ragged feature batches and the conv's exact integer oracle."""
 import os
 import subprocess
 import sys
