@@ -14,7 +14,7 @@ DEV = "cuda:0"
 def _batch(sizes, seed):
     rng = np.random.default_rng(seed)
     hmax, wmax = max(h for h, _ in sizes), max(w for _, w in sizes)
-    buf = np.zeros((len(sizes), hmax, wmax, 3), dtype=np.uint8)
+    buf = np.full((len(sizes), hmax, wmax, 3), 255, dtype=np.uint8)     # padding that is not Image.rotate's black fill: a stray tap shows
     imgs = []
     for i, (h, w) in enumerate(sizes):
         # smooth structure + noise: exercises the resample filter and the enhancers' clipping

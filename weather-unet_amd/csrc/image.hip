@@ -15,6 +15,13 @@
 // image exists except the 8-bit S x S staging buffer the colour jitter works on.
 #include "wu_common.h"
 
+// Every floating-point operation below is one IEEE operation, in the order written.  hipcc contracts a * b + c into one fused
+// multiply-add by default, which rounds once; Pillow's Blend.c rounds the product and then the sum, and at factors whose float sits
+// just above a short rational (0.8, 1.1, 1.2, 2/3, 4/3, ...) the single rounding lands on the other side of an integer for about one
+// byte in a hundred (tests/test_input_edges_cpu.py counts them).  The double arithmetic of the resample coefficients gets the same
+// guarantee: Resample.c rounds (xx + 0.5) * scale before it subtracts the support.
+#pragma clang fp contract(off)
+
 namespace {
 
 constexpr int kPrec = 22;          // Resample.c PRECISION_BITS = 32 - 8 - 2
@@ -140,7 +147,7 @@ __global__ __launch_bounds__(256) void image_geometry_kernel(const uint8_t* __re
 // ---- colour jitter: one workgroup per image, the three enhancers in the image's own random order -----------------------------
 __device__ __forceinline__ int grey_l(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }   // Convert.c rgb2l
 __device__ __forceinline__ int blend8(int degenerate, int v, float alpha) {                                                  // Blend.c
-    const float t = (float)degenerate + alpha * ((float)v - (float)degenerate);
+    const float t = (float)degenerate + alpha * ((float)v - (float)degenerate);          // two roundings (contraction is off, see the top)
     if (alpha >= 0.f && alpha <= 1.f) return (int)(uint8_t)t;
     return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)(uint8_t)t);
 }
