@@ -499,6 +499,48 @@ int wu_jpeg_reconstruct(const int16_t* coef_dev, const void* desc_dev, const int
                         void* workspace, size_t workspace_bytes, uint8_t* out_u8, int N, int Hmax, int Wmax, int n_tiles,
                         void* stream);
 
+/* ---- Huffman decoding of the scan on the device (csrc/jpeg_huff.hip): fills the coefficient buffer wu_jpeg_reconstruct consumes ----
+ * What goes over the link is the compressed scan, not the zero-filled coefficients.  HOST half: wu_jpeg_scan_stage copies the
+ * entropy-coded bytes of a file wu_jpeg_parse reported supported -- byte stuffing removed, split at the RSTn markers -- and the raw
+ * tables into caller-owned memory (re-entrant, no allocation, no GPU).  DEVICE half: wu_jpeg_huff_decode, one 256-thread workgroup per
+ * image, a self-synchronising walk over subsequences of `subseq_bits` bits (a multiple of 32 in [64, 4096]).
+ *
+ * A "segment" is one restart interval (the whole scan without DRI); it starts on a subseq_bits boundary of the image's scan region
+ * and is padded with zero bytes; every segment owns at least one subsequence.  Segment record: int32 first_subseq, bit_length,
+ * first_mcu, mcu_count.  Tables: 6 records of 272 bytes per image (16 counts + 256 values; DC of component 0, 1, 2, then AC of
+ * component 0, 1, 2; zero where unused); 3 x 64 uint16 quantisation tables in natural order as wu_jpeg_entropy_decode writes them.
+ * Status word of an image: 0 = its blocks and tables equal wu_jpeg_entropy_decode's; WU_JPEG_MAGNITUDE = decoded, over the bound;
+ * otherwise an OR of the WU_JPEG_HUFF_* bits (corrupt entropy-coded data: decode the file elsewhere). */
+#define WU_JPEG_HUFF_BAD_CODE 0x100      /* no table entry matches */
+#define WU_JPEG_HUFF_DC_CATEGORY 0x200   /* DC category > 15 */
+#define WU_JPEG_HUFF_INDEX 0x400         /* coefficient index past 63 */
+#define WU_JPEG_HUFF_SHORT 0x800         /* a segment ended before its MCU count was reached (or does not end where its last MCU ends) */
+#define WU_JPEG_HUFF_DC_RANGE 0x1000     /* a DC value outside int16 */
+#define WU_JPEG_HUFF_DEFAULT_SUBSEQ_BITS 1024
+typedef struct wu_jpeg_scan {
+    int scan_bytes;                  /* bytes written to scan_out: a multiple of 16, the last 8 are zero padding */
+    int n_segments, n_subseq;
+    int reserved;
+} wu_jpeg_scan;
+/* Upper bound of wu_jpeg_scan.scan_bytes for a file of nbytes bytes (0: not staged -- unsupported info, a bad subseq_bits, or more
+ * than 2^28 bytes, beyond which bit positions would leave 32 bits); wu_jpeg_scan_segments: the exact number of segment records. */
+size_t wu_jpeg_scan_stage_bytes(const wu_jpeg_info* info, size_t nbytes, int subseq_bits);
+int wu_jpeg_scan_segments(const wu_jpeg_info* info);
+/* Returns 0, or a negative code with a message: -1 arguments / capacity, -2 corrupt Huffman table, -3 bad restart marker sequence. */
+int wu_jpeg_scan_stage(const uint8_t* data, size_t nbytes, const wu_jpeg_info* info, int subseq_bits, uint8_t* scan_out,
+                       size_t scan_capacity, int* seg_out, size_t seg_capacity_bytes, uint8_t* dht_out1632, uint16_t* qtab_out192,
+                       wu_jpeg_scan* result);
+/* hdesc_dev: N records of wu_jpeg_huff_desc_bytes() (= 64) bytes, built by the caller from wu_jpeg_parse / wu_jpeg_scan_stage results:
+ *     int32 scan_off (bytes into scan_dev, a multiple of 16), scan_bytes, first_seg, n_segments, n_subseq, first_block, nblocks, ncomp,
+ *           hs0, vs0, mcus_x, total_mcus, pad[4];       n_subseq = 0: nothing to decode (an image decoded elsewhere)
+ * dht_dev: N x 1632 bytes, qtab_dev: N x 3 x 64 uint16, coef_dev: image n's nblocks blocks at first_block, status_dev: N int32.
+ * Zeroes exactly the images' blocks, decodes, turns DC differences into values and takes the magnitude bound: three launches whatever
+ * N is.  Nothing outside [first_block, first_block + nblocks) of an image is written.  Stream-ordered, no allocation, no
+ * synchronisation. */
+size_t wu_jpeg_huff_desc_bytes(void);
+int wu_jpeg_huff_decode(const uint8_t* scan_dev, const int* seg_dev, const uint8_t* dht_dev, const void* hdesc_dev,
+                        const uint16_t* qtab_dev, int16_t* coef_dev, int* status_dev, int N, int subseq_bits, void* stream);
+
 /* ---- JPEG encoding (inference/inf_transfer_c.py:119-120, inf_transfer_e.py:141-142, inf_1year_signals.py:105: save_image(x, '....jpg',
  * normalize=True), i.e. one Pillow Image.save(path) per output image with Pillow's defaults) -------------------------------------
  * Baseline JPEG (SOF0, one interleaved scan, the Annex K Huffman tables, no restart markers), YCbCr 4:2:0 or 4:4:4, quality 1..100,

@@ -113,6 +113,11 @@ SIGNATURES = {
     "wu_jpeg_desc_bytes": (SZ, []),
     "wu_jpeg_workspace_bytes": (SZ, [ctypes.c_longlong]),
     "wu_jpeg_reconstruct": (I, [P, P, P, P, P, SZ, P, I, I, I, I, P]),
+    "wu_jpeg_scan_stage_bytes": (SZ, [P, SZ, I]),
+    "wu_jpeg_scan_segments": (I, [P]),
+    "wu_jpeg_scan_stage": (I, [P, SZ, P, I, P, SZ, P, SZ, P, P, P]),
+    "wu_jpeg_huff_desc_bytes": (SZ, []),
+    "wu_jpeg_huff_decode": (I, [P, P, P, P, P, P, P, I, I, P]),
     "wu_jpeg_enc_header_bytes": (SZ, []),
     "wu_jpeg_enc_header": (I, [I, I, I, I, P, SZ]),
     "wu_jpeg_enc_qtables": (I, [I, P]),

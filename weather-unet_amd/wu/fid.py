@@ -128,11 +128,12 @@ def image_files(path):
     return sorted(list(p.glob("*.jpg")) + list(p.glob("*.png")))
 
 
-def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False):
+def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False):
     """(mu, sigma) of a .npz file or of the images in a directory (uint8 batches straight to the GPU).  gpu_decode: read the files
     through wu.jpeg.GPUJpegDecoder instead of the per-file Pillow loop; gpu_decode_png: through wu.png.GPUPngDecoder, which inflates the
     segmented PNGs wu.png_enc writes on the GPU and hands every other file to Pillow -- the same uint8 batch, hence the same statistics.
-    Both off by default."""
+    gpu_entropy (implies gpu_decode): the JPEG decoder also Huffman-decodes on the GPU (``entropy="device"``).  All off by default."""
+    gpu_decode = gpu_decode or gpu_entropy
     if path.endswith(".npz"):
         with np.load(path) as f:
             return f["mu"][:], f["sigma"][:]
@@ -147,7 +148,7 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png
             dec = png.GPUPngDecoder()
         else:
             from .jpeg import GPUJpegDecoder
-            dec = GPUJpegDecoder()
+            dec = GPUJpegDecoder(entropy="device" if gpu_entropy else "host")
         try:
             for i in range(0, len(files), batch_size):
                 batch, sizes = dec.decode_batch(files[i:i + batch_size])
@@ -163,7 +164,8 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png
     return stats.finalize()
 
 
-def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False):
+def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                              gpu_entropy=False):
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError(f"Invalid path: {p}")
@@ -171,8 +173,8 @@ def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precisio
     if not all(p.endswith(".npz") for p in paths):
         model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], precision=precision)
         model.load_state_dict(torch.load(weights, map_location="cpu"))
-    m1, s1 = statistics_of_path(paths[0], model, batch_size, gpu_decode, gpu_decode_png)
-    m2, s2 = statistics_of_path(paths[1], model, batch_size, gpu_decode, gpu_decode_png)
+    m1, s1 = statistics_of_path(paths[0], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy)
+    m2, s2 = statistics_of_path(paths[1], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy)
     return calculate_frechet_distance(m1, s1, m2, s2)
 
 
@@ -185,10 +187,14 @@ def main(argv=None):
     ap.add_argument("--dims", type=int, default=2048, choices=list(InceptionV3.BLOCK_INDEX_BY_DIM))
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--gpu-decode", action="store_true", help="decode the image files with wu.jpeg.GPUJpegDecoder (HIP kernels) instead of Pillow")
+    ap.add_argument("--gpu-entropy", action="store_true",
+                    help="with --gpu-decode (implied): Huffman-decode the JPEG scans on the GPU too, so that the compressed scan and not the "
+                         "coefficients goes over the link")
     ap.add_argument("--gpu-decode-png", action="store_true",
                     help="decode segmented PNG files (what wu.png_enc writes) with wu.png.GPUPngDecoder (HIP kernels); other files go to Pillow")
     args = ap.parse_args(argv)
-    fid = calculate_fid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png)
+    fid = calculate_fid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png,
+                                    args.gpu_entropy)
     print(f"FID: {fid}")
     return 0
 

@@ -11,7 +11,11 @@ same worker thread, counted in ``stats`` and copied into its slot: the batch is 
     src_u8, sizes = dec.decode_batch(paths_or_bytes)
     images = GPUInputPipeline(224, ...)(src_u8, sizes)
 
-``parse`` and ``entropy_decode`` are host-only and work without a GPU.
+``GPUJpegDecoder(entropy="device")`` moves the Huffman decoding to the GPU as well (csrc/jpeg_huff.hip): the host only copies the
+entropy-coded bytes of every file into the staging buffer (``scan_stage``), the compressed scan goes over the link instead of two bytes
+per sample of coefficients, and ``finish`` waits once per batch for the device's verdict on every image.  Opt-in; the default is "host".
+
+``parse``, ``entropy_decode`` and ``scan_stage`` are host-only and work without a GPU.
 """
 import ctypes
 import threading
@@ -27,6 +31,9 @@ from .layout import stream_ptr
 MODE_GREY, MODE_444, MODE_H2V1, MODE_H2V2 = 0, 1, 2, 3
 REASONS = {0: "ok", 1: "not-jpeg", 2: "corrupt-header", 3: "progressive", 4: "arithmetic", 5: "precision", 6: "lossless",
            7: "colorspace", 8: "qtable16", 9: "sampling", 10: "multiscan", 11: "magnitude"}
+HUFF_STATUS = {0: "ok", 11: "magnitude"}          # a device status word by name; every other value: "corrupt-scan"
+DHT_BYTES = 6 * 272       # raw DHT records of one image (csrc/jpeg_huff.hip kDhtImage)
+DEFAULT_SUBSEQ_BITS = 1024          # WU_JPEG_HUFF_DEFAULT_SUBSEQ_BITS: the lowest kernel time of 256 / 512 / 1024 / 2048 (profiles/jpeg_huff_bench.md)
 TILE_BLOCKS = 32          # blocks per IDCT workgroup (csrc/jpeg.hip kTileBlocks)
 MAX_NATIVE_PIXELS = 89478485          # Pillow's Image.MAX_IMAGE_PIXELS default: larger images go through Pillow (which warns or refuses)
 
@@ -48,6 +55,15 @@ class JpegInfo(ctypes.Structure):
     def sampling(self):
         """[(h, v)] per component."""
         return [(self.hs[c], self.vs[c]) for c in range(min(self.ncomp, 3))]
+
+
+class JpegScan(ctypes.Structure):
+    """wu_jpeg_scan of include/wu_kernels.h."""
+    _fields_ = [("scan_bytes", ctypes.c_int), ("n_segments", ctypes.c_int), ("n_subseq", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+def huff_status_name(code):
+    return HUFF_STATUS.get(int(code), "corrupt-scan")
 
 
 class JpegUnsupported(ValueError):
@@ -104,6 +120,40 @@ def entropy_decode(data):
     return planes, qtabs, info
 
 
+def _stage_into(lib, data, info, subseq_bits, scan_ptr, scan_cap, seg_ptr, seg_cap, dht_ptr, qtab_ptr):
+    """wu_jpeg_scan_stage into caller-owned memory; returns the JpegScan, raises JpegError on a refusal."""
+    res = JpegScan()
+    rc = lib.wu_jpeg_scan_stage(data, len(data), ctypes.byref(info), subseq_bits, scan_ptr, scan_cap, seg_ptr, seg_cap, dht_ptr, qtab_ptr,
+                                ctypes.byref(res))
+    if rc < 0:
+        msg = lib.wu_last_error()
+        raise JpegError(msg.decode() if msg else f"wu_jpeg_scan_stage failed ({rc})")
+    return res
+
+
+def scan_stage(data, subseq_bits=DEFAULT_SUBSEQ_BITS):
+    """Host staging alone (tests, tools): what ``entropy="device"`` uploads for one file.  Returns a dict: ``scan`` (uint8 array: the
+    entropy-coded bytes, stuffing removed, every restart interval padded to whole subsequences), ``segs`` ((n, 4) int32: first_subseq,
+    bit_length, first_mcu, mcu_count), ``dht`` (1632 bytes), ``qtab`` ((3, 64) uint16, natural order), ``n_subseq``, ``bound`` (what
+    wu_jpeg_scan_stage_bytes promised) and ``info``.  Raises JpegUnsupported / JpegError."""
+    lib = _lib.load()
+    data = _codec.read(data)
+    info = _parse_bytes(lib, data)
+    if not info.supported:
+        raise JpegUnsupported(info.reason_name)
+    bound = int(lib.wu_jpeg_scan_stage_bytes(ctypes.byref(info), len(data), int(subseq_bits)))
+    nseg = int(lib.wu_jpeg_scan_segments(ctypes.byref(info)))
+    if bound == 0 or nseg == 0:
+        raise JpegUnsupported("too-large", f"no staging bound at subseq_bits={subseq_bits}")
+    scan = np.zeros(bound, np.uint8)
+    segs = np.zeros((nseg, 4), np.int32)
+    dht = np.zeros(DHT_BYTES, np.uint8)
+    qtab = np.zeros((3, 64), np.uint16)
+    res = _stage_into(lib, data, info, int(subseq_bits), scan.ctypes.data, scan.nbytes, segs.ctypes.data, segs.nbytes, dht.ctypes.data,
+                      qtab.ctypes.data)
+    return dict(scan=scan[:res.scan_bytes], segs=segs, dht=dht, qtab=qtab, n_subseq=res.n_subseq, bound=bound, info=info)
+
+
 class HostBatch(_codec.HostBatch):
     """Result of GPUJpegDecoder.prepare: entropy-decoded coefficients and descriptors of one batch in a staging buffer.  It owns
     the buffer until it is released (``release()`` or garbage collection), so it may be finished more than once."""
@@ -116,13 +166,18 @@ class HostBatch(_codec.HostBatch):
         self.off = {}
         self.fallbacks = []       # (slot, (h, w, 3) uint8 array) decoded by Pillow
         self.names = []
+        self.entropy = "host"
+        self.datas = []           # device entropy: the file bytes of the images the device may yet reject (None: settled in prepare)
+        self.counted = False      # ... and whether their verdicts are in the decoder's stats already
+        self.last_status = []     # per image: "ok", or the reason it was decoded by Pillow
 
 
 class DeviceBatch:
     """The uploaded coefficients, tables and descriptors of one batch plus the plane workspace: the arguments of wu_jpeg_reconstruct."""
-    def __init__(self, buf, off, workspace, n, hmax, wmax, n_tiles):
+    def __init__(self, buf, off, workspace, n, hmax, wmax, n_tiles, coef=None):
         self.buf, self.off, self.workspace = buf, off, workspace
         self.n, self.hmax, self.wmax, self.n_tiles = n, hmax, wmax, n_tiles
+        self.coef = coef          # device entropy: the device-only coefficient buffer (host entropy: they are part of ``buf``)
 
 
 class GPUJpegDecoder:
@@ -137,8 +192,21 @@ class GPUJpegDecoder:
     Every buffer carries an event recorded right after its copy; ``prepare`` takes a buffer only if no HostBatch holds it and its
     event has completed (checked with ``query()`` on the host, never waited for on the GPU), and allocates another one otherwise.
     Past ``max_staging`` buffers it blocks the HOST on the oldest event instead of growing further.
+
+    ``entropy="device"`` (default "host": the path above, untouched): ``prepare`` parses and copies every file's entropy-coded bytes,
+    segment table and raw tables into the staging buffer ([scan bytes | segment tables | DHT | qtab | Huffman desc | desc | tile map]);
+    ``finish`` uploads that, runs wu_jpeg_huff_decode (subsequences of ``subseq_bits`` bits) into a device-only coefficient buffer and
+    wu_jpeg_reconstruct, then copies the N status words back and waits for them -- ONE host synchronisation per batch, the rule of
+    ``wu.png.GPUPngDecoder.finish``: whether the device accepted an image is known only then.  An image it rejects is decoded by Pillow
+    into its slot and counted in ``stats`` under the status name ("magnitude", "corrupt-scan").
     """
-    def __init__(self, device="cuda", threads=None, max_staging=8):
+    def __init__(self, device="cuda", threads=None, max_staging=8, entropy="host", subseq_bits=None):
+        if entropy not in ("host", "device"):
+            raise ValueError(f"GPUJpegDecoder: entropy must be 'host' or 'device', got {entropy!r}")
+        self.entropy = entropy
+        self.subseq_bits = DEFAULT_SUBSEQ_BITS if subseq_bits is None else int(subseq_bits)
+        if self.subseq_bits % 32 or not 64 <= self.subseq_bits <= 4096:
+            raise ValueError(f"GPUJpegDecoder: subseq_bits must be a multiple of 32 in [64, 4096], got {subseq_bits}")
         self.threads = _codec.worker_threads(threads)
         self.device = torch.device(device)
         self.max_staging = int(max_staging)
@@ -148,6 +216,7 @@ class GPUJpegDecoder:
         self.stats = {"native": 0, "fallback": 0, "fallback_reasons": {}}
         self._lib = _lib.load()
         assert self._lib.wu_jpeg_info_bytes() == ctypes.sizeof(JpegInfo) and self._lib.wu_jpeg_desc_bytes() == 64
+        assert self._lib.wu_jpeg_huff_desc_bytes() == 64
 
     def close(self):
         self._pool.shutdown(wait=True)
@@ -171,6 +240,8 @@ class GPUJpegDecoder:
         hb = HostBatch(self._staging)
         hb.n = n = len(items)
         hb.names = [_codec.name(it, i) for i, it in enumerate(items)]
+        if self.entropy == "device":
+            return self._prepare_device(hb, opened)
         first_block, first_tile, tiles = [0] * n, [0] * n, 0
         for i, (_, info, rgb, _) in enumerate(opened):
             first_tile[i], first_block[i] = tiles, tiles * TILE_BLOCKS
@@ -204,6 +275,7 @@ class GPUJpegDecoder:
         results = list(self._pool.map(decode, range(n)))
         for i, ((_, info, _, _), (rgb, reason)) in enumerate(zip(opened, results)):
             _codec.count(self.stats, self._lock, reason)
+            hb.last_status.append(reason or "ok")
             if rgb is not None:
                 hb.fallbacks.append((i, rgb))
                 hb.sizes.append((int(rgb.shape[0]), int(rgb.shape[1])))
@@ -218,6 +290,78 @@ class GPUJpegDecoder:
         hb.hmax, hb.wmax = max(h for h, _ in hb.sizes), max(w for _, w in hb.sizes)
         return hb
 
+    def _prepare_device(self, hb, opened):
+        """The device-entropy half of ``prepare``: stage the scans instead of decoding them."""
+        n, S, lib = hb.n, self.subseq_bits, self._lib
+        hb.entropy = "device"
+        opened = list(opened)
+        bound, nseg = [0] * n, [0] * n
+        for i, (data, info, rgb, reason) in enumerate(opened):
+            if rgb is None:
+                bound[i] = int(lib.wu_jpeg_scan_stage_bytes(ctypes.byref(info), len(data), S))
+                nseg[i] = int(lib.wu_jpeg_scan_segments(ctypes.byref(info)))
+                if bound[i] == 0 or nseg[i] == 0:                      # a scan of more than 2^28 bytes
+                    opened[i] = (data, info, _codec.pillow_rgb(data, hb.names[i]), "too-large")
+        scan_off, first_seg, first_block, first_tile = [0] * n, [0] * n, [0] * n, [0] * n
+        at = segs = tiles = 0
+        for i, (_, info, rgb, _) in enumerate(opened):
+            scan_off[i], first_seg[i], first_tile[i], first_block[i] = at, segs, tiles, tiles * TILE_BLOCKS
+            if rgb is None:
+                at += bound[i]                                         # a multiple of 16
+                segs += nseg[i]
+                tiles += (info.total_blocks + TILE_BLOCKS - 1) // TILE_BLOCKS
+        off = {"scan": 0}
+        off["seg"] = _codec.align(max(at, 16))
+        off["dht"] = _codec.align(off["seg"] + max(segs, 1) * 16)
+        off["qtab"] = _codec.align(off["dht"] + n * DHT_BYTES)
+        off["hdesc"] = _codec.align(off["qtab"] + n * 384)
+        off["desc"] = _codec.align(off["hdesc"] + n * 64)
+        off["tile"] = _codec.align(off["desc"] + n * 64)
+        hb.used = _codec.align(off["tile"] + max(tiles, 1) * 4)
+        hb.off, hb.n_tiles = off, tiles
+        st = hb.staging = self._staging.acquire(hb.used)
+        hdesc = st.array[off["hdesc"]:off["hdesc"] + n * 64].view(np.int32).reshape(n, 16)
+        desc = st.array[off["desc"]:off["desc"] + n * 64].view(np.int32).reshape(n, 16)
+        tile = st.array[off["tile"]:off["tile"] + max(tiles, 1) * 4].view(np.int32)
+        hdesc[:] = 0
+        desc[:] = 0
+        tile[:] = 0
+
+        def stage(i):
+            data, info, rgb, reason = opened[i]
+            if rgb is not None:
+                return rgb, reason, None
+            try:
+                res = _stage_into(lib, data, info, S, st.ptr + off["scan"] + scan_off[i], bound[i], st.ptr + off["seg"] + first_seg[i] * 16,
+                                  nseg[i] * 16, st.ptr + off["dht"] + i * DHT_BYTES, st.ptr + off["qtab"] + i * 384)
+            except JpegError:
+                return _codec.pillow_rgb(data, hb.names[i]), "corrupt-scan", None      # Pillow is the arbiter; it raises on a truncated file
+            return None, None, res
+
+        results = list(self._pool.map(stage, range(n)))
+        for i, ((data, info, _, _), (rgb, reason, res)) in enumerate(zip(opened, results)):
+            if rgb is not None:
+                _codec.count(self.stats, self._lock, reason)
+                hb.last_status.append(reason)
+                hb.datas.append(None)
+                hb.fallbacks.append((i, rgb))
+                hb.sizes.append((int(rgb.shape[0]), int(rgb.shape[1])))
+                desc[i, 0], desc[i, 8] = first_block[i], first_tile[i]     # h = w = nblocks = 0, no subsequences: nothing is decoded
+                hdesc[i, 5] = first_block[i]
+                continue
+            hb.last_status.append("ok")
+            hb.datas.append(data)
+            hb.sizes.append((info.height, info.width))
+            nt = (info.total_blocks + TILE_BLOCKS - 1) // TILE_BLOCKS
+            bw_c, bh_c = (info.blocks_w[1], info.blocks_h[1]) if info.ncomp == 3 else (0, 0)
+            desc[i, :10] = (first_block[i], info.height, info.width, info.mode, info.blocks_w[0], info.blocks_h[0], bw_c, bh_c,
+                            first_tile[i], info.total_blocks)
+            hdesc[i, :13] = (scan_off[i], res.scan_bytes, first_seg[i], res.n_segments, res.n_subseq, first_block[i], info.total_blocks,
+                             info.ncomp, info.hs[0], info.vs[0], info.mcus_x, info.mcus_x * info.mcus_y, info.restart_interval)
+            tile[first_tile[i]:first_tile[i] + nt] = i
+        hb.hmax, hb.wmax = max(h for h, _ in hb.sizes), max(w for _, w in hb.sizes)
+        return hb
+
     # ---- device stage ----
     def upload(self, hb):
         """One non-blocking H2D copy of the used part of the staging buffer (the event guarding the buffer is recorded after it)."""
@@ -227,7 +371,21 @@ class GPUJpegDecoder:
         with torch.cuda.device(self.device):                          # the copy and its event go to this device's current stream
             buf = _codec.upload(hb, self.device, "GPUJpegDecoder")
             ws = torch.empty(max(int(self._lib.wu_jpeg_workspace_bytes(hb.n_tiles * TILE_BLOCKS)), 256), dtype=torch.uint8, device=self.device)
-        return DeviceBatch(buf, hb.off, ws, hb.n, hb.hmax, hb.wmax, hb.n_tiles)
+            coef = None
+            if hb.entropy == "device":                                 # never uploaded: wu_jpeg_huff_decode fills it
+                coef = torch.empty(max(hb.n_tiles * TILE_BLOCKS * 128, 256), dtype=torch.uint8, device=self.device)
+        return DeviceBatch(buf, hb.off, ws, hb.n, hb.hmax, hb.wmax, hb.n_tiles, coef)
+
+    def huff_decode(self, db):
+        """wu_jpeg_huff_decode on the current stream (device entropy); returns the (N,) int32 CUDA tensor of status words."""
+        if db.coef is None:
+            raise ValueError("GPUJpegDecoder.huff_decode: this batch was prepared with entropy='host'")
+        base = db.buf.data_ptr()
+        with torch.cuda.device(db.buf.device):
+            status = torch.empty(db.n, dtype=torch.int32, device=db.buf.device)
+            _lib.call("wu_jpeg_huff_decode", base + db.off["scan"], base + db.off["seg"], base + db.off["dht"], base + db.off["hdesc"],
+                      base + db.off["qtab"], db.coef.data_ptr(), status.data_ptr(), db.n, self.subseq_bits, stream_ptr())
+        return status
 
     def reconstruct(self, db, out=None):
         """wu_jpeg_reconstruct on the current stream; ``out``: an (N, Hmax, Wmax, 3) uint8 CUDA tensor to fill (allocated if None)."""
@@ -236,23 +394,49 @@ class GPUJpegDecoder:
         if tuple(out.shape) != (db.n, db.hmax, db.wmax, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
             raise ValueError("GPUJpegDecoder.reconstruct: out must be a contiguous (N, Hmax, Wmax, 3) uint8 CUDA tensor")
         base = db.buf.data_ptr()
+        coef_ptr = db.coef.data_ptr() if db.coef is not None else base + db.off["coef"]
         with torch.cuda.device(db.buf.device):
-            _lib.call("wu_jpeg_reconstruct", base + db.off["coef"], base + db.off["desc"], base + db.off["tile"], base + db.off["qtab"],
+            _lib.call("wu_jpeg_reconstruct", coef_ptr, base + db.off["desc"], base + db.off["tile"], base + db.off["qtab"],
                       db.workspace.data_ptr(), db.workspace.numel(), out.data_ptr(), db.n, db.hmax, db.wmax, db.n_tiles, stream_ptr())
         return out
 
     def finish(self, hb):
         """Upload + reconstruct + the Pillow-decoded slots; returns (src_u8 (N, Hmax, Wmax, 3) uint8 CUDA, [(h, w)] * N)."""
         db = self.upload(hb)
-        out = self.reconstruct(db)
+        late = []
+        if hb.entropy == "device":
+            status = self.huff_decode(db)
+            out = self.reconstruct(db)
+            codes = status.cpu().numpy()                               # waits for the kernels: a rejection is known only now
+            for i, code in enumerate(codes):
+                if hb.datas[i] is None:
+                    continue
+                name = huff_status_name(code)
+                if not hb.counted:
+                    _codec.count(self.stats, self._lock, None if code == 0 else name)
+                hb.last_status[i] = name
+                if code == 0:
+                    continue
+                rgb = _codec.pillow_rgb(hb.datas[i], hb.names[i])          # Pillow is the arbiter; it raises on a truncated file
+                if rgb.shape[:2] != hb.sizes[i]:
+                    raise RuntimeError(f"cannot decode image {hb.names[i]}: Pillow reads {rgb.shape[1]} x {rgb.shape[0]}, the header "
+                                       f"says {hb.sizes[i][1]} x {hb.sizes[i][0]}")
+                late.append((i, rgb))
+            hb.counted = True
+        else:
+            out = self.reconstruct(db)
         with torch.cuda.device(self.device):
-            for slot, rgb in hb.fallbacks:                             # the second, small H2D path: after the kernels zeroed the slot
+            for slot, rgb in hb.fallbacks + late:                      # the second, small H2D path: over whatever the kernels left in the slot
                 out[slot, :rgb.shape[0], :rgb.shape[1]] = torch.from_numpy(rgb).to(self.device)
         return out, list(hb.sizes)
 
-    def decode_batch(self, items):
+    def decode_batch(self, items, return_status=False):
+        """(src_u8, sizes), and with ``return_status`` a third item as in ``wu.png``: per image "ok", or the reason Pillow decoded it."""
         hb = self.prepare(items)
         try:
-            return self.finish(hb)
+            out, sizes = self.finish(hb)
         finally:
             hb.release()
+        if return_status:
+            return out, sizes, list(hb.last_status)
+        return out, sizes
