@@ -747,6 +747,19 @@ int wu_inception_input(const void* src, int src_u8, int N, int Hin, int Win, flo
  * MFMA chains over b, the cross-batch sums fp64: mu = K + sum / n, sigma = (cross - sum sum^T / n) / (n - 1). */
 int wu_feature_stats_update(const float* x, int ldx, int B, int D, float* shift, int init_shift, double* sum, double* cross, void* stream);
 
+/* ---- Kernel Inception Distance (wu/kid.py): the unbiased polynomial-kernel MMD^2 of S subsets of m rows of two feature banks -----------
+ * x (n1 x D fp32, row stride ldx) and y (n2 x D, ldy) are the banks; idx (S, 2, m) int32 on the device holds, per subset, the m row
+ * positions into x and then the m into y (values are clamped into the bank by the kernel; validate them before upload).  With
+ *     k(a, b) = (gamma <a, b> + coef0)^degree      in fp64 on the rows widened to fp64, the power by repeated multiplication,
+ *     sums[3 s + 0] = sxx = sum_{i != j} k(x_i, x_j),   sums[3 s + 1] = syy likewise,   sums[3 s + 2] = sxy = sum_{i, j} k(x_i, y_j),
+ *     mmd2[s] = (sxx + syy) / (m (m - 1)) - 2 sxy / (m m).
+ * Two launches for all S subsets: 64 x 64 tiles on the fp64 matrix cores (upper-triangular tiles of xx / yy, every tile of xy), each
+ * reduced to one double in `workspace` in a fixed order, then one wave per subset.  No atomics: the same inputs give the same bits.
+ * Stream-ordered, caller-owned buffers, no allocation, no synchronisation.  m >= 2, m <= min(n1, n2), degree >= 1, S <= 65535, ld >= D. */
+size_t wu_kid_workspace_bytes(int S, int m);      /* 0 for S or m out of range */
+int wu_kid_mmd(const float* x, int ldx, int n1, const float* y, int ldy, int n2, const int* idx, int S, int m, int D, int degree,
+               double gamma, double coef0, void* workspace, double* sums, double* mmd2, void* stream);
+
 /* layout helpers for the module boundary: NHWC `dtype` <-> NCHW fp32 (feature maps returned by
  * SNDisc.forward, disc.py:38; gradients flowing back into them). */
 int wu_nhwc_to_nchw_f32(const void* x, int ldx, float* y_nchw, int N, int H, int W, int C, int dtype, void* stream);

@@ -9,6 +9,11 @@ downloaded.
 Feature statistics never leave the GPU per batch: ``FIDStatistics.update`` runs the network and adds the batch's shifted first and second
 moments into fp64 device accumulators (wu_feature_stats_update); ``finalize`` turns them into ``mu`` and the unbiased ``sigma``
 (np.cov(rowvar=False)).  The Frechet distance itself (a matrix square root of a D x D product) runs on the host in float64 with scipy.
+
+``--kid`` adds the Kernel Inception Distance (wu.kid: the unbiased polynomial-kernel MMD^2 over random subsets of the same feature rows,
+on the fp64 matrix cores), the metric to read on a few hundred images, where the covariance above is rank-deficient.  It needs the rows
+themselves: a ``.npz`` PATH must then hold ``features`` (``wu.kid.FeatureBank.save_npz``); ``mu`` / ``sigma`` are computed from the rows
+when the file lacks them.
 """
 import argparse
 import os
@@ -34,7 +39,8 @@ class FIDStatistics:
         self.n = 0
         self._sum = self._cross = self._shift = None
 
-    def update(self, images, value_range=(0, 1)):
+    def update(self, images, value_range=(0, 1), features=None):
+        """``features``: a wu.kid.FeatureBank that also receives the batch's rows (for the KID)."""
         feat = self.model(images, value_range=value_range)[0]
         n, c, h, w = feat.shape
         if h * w != 1 or feat.dtype != torch.float32:
@@ -42,6 +48,8 @@ class FIDStatistics:
         else:
             feat = feat.permute(0, 2, 3, 1).reshape(n, c)          # the (N, 1, 1, C) buffer itself
         self.update_features(feat)
+        if features is not None:
+            features.append(feat)
 
     def update_features(self, feats):
         """Add a batch of feature rows (B, D) float32 on the GPU."""
@@ -128,15 +136,19 @@ def image_files(path):
     return sorted(list(p.glob("*.jpg")) + list(p.glob("*.png")))
 
 
-def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False):
+def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False, features=None):
     """(mu, sigma) of a .npz file or of the images in a directory (uint8 batches straight to the GPU).  gpu_decode: read the files
     through wu.jpeg.GPUJpegDecoder instead of the per-file Pillow loop; gpu_decode_png: through wu.png.GPUPngDecoder, which inflates the
     segmented PNGs wu.png_enc writes on the GPU and hands every other file to Pillow -- the same uint8 batch, hence the same statistics.
-    gpu_entropy (implies gpu_decode): the JPEG decoder also Huffman-decodes on the GPU (``entropy="device"``).  All off by default."""
+    gpu_entropy (implies gpu_decode): the JPEG decoder also Huffman-decodes on the GPU (``entropy="device"``).  All off by default.
+    features: a wu.kid.FeatureBank that also receives every feature row (the KID's input); a .npz must then hold ``features``, and its
+    ``mu`` / ``sigma`` are taken from the file when it has them and computed from the rows when it does not."""
     gpu_decode = gpu_decode or gpu_entropy
     if path.endswith(".npz"):
-        with np.load(path) as f:
-            return f["mu"][:], f["sigma"][:]
+        if features is None:
+            with np.load(path) as f:
+                return f["mu"][:], f["sigma"][:]
+        return _npz_statistics_and_features(path, features)
     from PIL import Image
     files = image_files(path)
     if not files:
@@ -154,14 +166,64 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png
                 batch, sizes = dec.decode_batch(files[i:i + batch_size])
                 if any(s != sizes[0] for s in sizes):
                     raise ValueError(f"images of different sizes in {path}: {sorted(set(sizes))}")       # np.stack's refusal below
-                stats.update(batch)
+                stats.update(batch, features=features)
         finally:
             dec.close()
         return stats.finalize()
     for i in range(0, len(files), batch_size):
         batch = np.stack([np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8) for f in files[i:i + batch_size]])
-        stats.update(torch.from_numpy(batch).cuda())
+        stats.update(torch.from_numpy(batch).cuda(), features=features)
     return stats.finalize()
+
+
+def _npz_statistics_and_features(path, features):
+    from .kid import FeatureBank
+    bank = FeatureBank.load_npz(path)
+    if bank.n:
+        features.append(bank.features)
+    with np.load(path) as f:
+        if "mu" in f and "sigma" in f:
+            return f["mu"][:], f["sigma"][:]
+    stats = FIDStatistics(None)
+    stats.update_features(bank.features)
+    return stats.finalize()
+
+
+def _inception_for(paths, weights, dims, precision):
+    for p in paths:
+        if not os.path.exists(p):
+            raise RuntimeError(f"Invalid path: {p}")
+    if all(p.endswith(".npz") for p in paths):
+        return None
+    model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], precision=precision)
+    model.load_state_dict(torch.load(weights, map_location="cpu"))
+    return model
+
+
+def calculate_fid_and_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                                      gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
+    """(fid, (kid_mean, kid_std)) from ONE pass over each path: the feature rows feed the moment accumulators and a FeatureBank."""
+    from .kid import FeatureBank, kernel_inception_distance
+    model = _inception_for(paths, weights, dims, precision)
+    banks = FeatureBank(), FeatureBank()
+    m1, s1 = statistics_of_path(paths[0], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=banks[0])
+    m2, s2 = statistics_of_path(paths[1], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=banks[1])
+    kid = kernel_inception_distance(banks[0], banks[1], num_subsets=num_subsets, subset_size=subset_size, seed=seed)
+    return calculate_frechet_distance(m1, s1, m2, s2), kid
+
+
+def calculate_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                              gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
+    """(mean, std) of the Kernel Inception Distance between two image directories / .npz files holding ``features``."""
+    from .kid import FeatureBank, kernel_inception_distance
+    model = _inception_for(paths, weights, dims, precision)
+    banks = FeatureBank(), FeatureBank()
+    for p, bank in zip(paths, banks):
+        if p.endswith(".npz"):
+            bank.append(FeatureBank.load_npz(p).features)
+        else:
+            statistics_of_path(p, model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=bank)
+    return kernel_inception_distance(banks[0], banks[1], num_subsets=num_subsets, subset_size=subset_size, seed=seed)
 
 
 def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
@@ -192,7 +254,21 @@ def main(argv=None):
                          "coefficients goes over the link")
     ap.add_argument("--gpu-decode-png", action="store_true",
                     help="decode segmented PNG files (what wu.png_enc writes) with wu.png.GPUPngDecoder (HIP kernels); other files go to Pillow")
+    ap.add_argument("--kid", action="store_true",
+                    help="also print the Kernel Inception Distance (mean and standard deviation over random subsets of the feature rows); "
+                         "a .npz path must then hold 'features'")
+    ap.add_argument("--kid-subsets", type=int, default=100, help="with --kid: number of subsets")
+    ap.add_argument("--kid-subset-size", type=int, default=1000,
+                    help="with --kid: rows per subset; an error, never clamped, when either path has fewer images")
+    ap.add_argument("--kid-seed", type=int, default=2020, help="with --kid: seed of the subset draw (numpy RandomState)")
     args = ap.parse_args(argv)
+    if args.kid:
+        fid, (kid_mean, kid_std) = calculate_fid_and_kid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision,
+                                                                     args.gpu_decode, args.gpu_decode_png, args.gpu_entropy,
+                                                                     args.kid_subsets, args.kid_subset_size, args.kid_seed)
+        print(f"FID: {fid}")
+        print(f"KID: {kid_mean} \u00b1 {kid_std}")
+        return 0
     fid = calculate_fid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png,
                                     args.gpu_entropy)
     print(f"FID: {fid}")
