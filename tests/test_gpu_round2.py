@@ -411,7 +411,12 @@ def test_fused_adam_updates_reach_the_convs():
 def test_gate_bit_producers_at_full_size():
     """The forward kernels that also write gate bits must produce the SAME activations as their plain forms at BASELINE size (B=32
     256x256): many iterations per wave / many tiles per workgroup, where the prefetch-and-counted-wait machinery is actually
-    exercised (a register-prefetch bug of the 3->64 kernel passed every small-shape test), and the bits must equal (y > 0)."""
+    exercised (a register-prefetch bug of the 3->64 kernel passed every small-shape test), and the bits must equal (y > 0).
+
+    What is compared is the gate-bit instance against the PLAIN instance of the same kernel, not against a reference: both share one
+    prefetch loop, so a fault in that loop shows in neither.  The comparison of either instance with an exact CPU oracle at more than
+    one iteration per wave is tests/test_gpu_thin_exact.py (test_fwd64_mfma_more_than_one_iteration_per_wave and
+    test_fwd64_gate_bits_more_than_one_iteration_per_wave); the persistent 64-channel convs have theirs in tests/test_gpu_conv_walk.py."""
     from wu import kernels as K
     from wu.layout import empty_nhwc, precision_code
     dev = torch.device("cuda")
