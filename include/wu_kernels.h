@@ -760,6 +760,23 @@ size_t wu_kid_workspace_bytes(int S, int m);      /* 0 for S or m out of range *
 int wu_kid_mmd(const float* x, int ldx, int n1, const float* y, int ldy, int n2, const int* idx, int S, int m, int D, int degree,
                double gamma, double coef0, void* workspace, double* sums, double* mmd2, void* stream);
 
+/* ---- Improved precision / recall and density / coverage (wu/prdc.py): k-NN radii and manifold-membership counts of two feature banks ----
+ * For fp32 rows a, b of width D widened to fp64:  d2(a, b) = max((|a|^2 + |b|^2) - 2 <a, b>, 0), every operation rounded on its own.
+ *   wu_knn_radii:   radii[i] = the (k + 1)-th smallest of { d2(x_i, x_j) : j < n } with d2(x_i, x_i) forced to 0 (the row itself counts).
+ *   wu_prdc_counts: A[i] = #{ j : d2(x_i, y_j) <= radii_x[i] },  B[i] = #{ j : d2(x_i, y_j) <= radii_y[j] }   (n1 values each),
+ *                   C[j] = #{ i : d2(x_i, y_j) <= radii_x[i] }                                                  (n2 values).
+ * 64 x 64 tiles of <a, b> on the fp64 matrix cores; no distance matrix and no tile of one reaches global memory.  wu_knn_radii runs a grid
+ * of (row tiles, col_splits): each workgroup keeps the k + 1 smallest d2 per row over the column tiles of its split, a finish launch merges
+ * the splits.  col_splits = 0 lets the library choose from n; 1..1024 forces that many (a split without columns contributes +inf).  The
+ * counts cross workgroups as integer atomic adds, the radii are order-independent: the same inputs give the same bits.
+ * workspace: wu_prdc_workspace_bytes(n1, n2, k, col_splits) bytes serve wu_knn_radii on either bank (with that k and col_splits) and
+ * wu_prdc_counts; 0 for arguments out of range.  Stream-ordered, caller-owned buffers, no allocation, no synchronisation.
+ * 1 <= k <= 16, k + 1 <= n <= 2^21, ld >= D >= 1. */
+size_t wu_prdc_workspace_bytes(int n1, int n2, int k, int col_splits);
+int wu_knn_radii(const float* x, int ldx, int n, int D, int k, int col_splits, void* workspace, double* radii, void* stream);
+int wu_prdc_counts(const float* x, int ldx, int n1, const double* radii_x, const float* y, int ldy, int n2, const double* radii_y, int D,
+                   void* workspace, unsigned* A, unsigned* B, unsigned* C, void* stream);
+
 /* layout helpers for the module boundary: NHWC `dtype` <-> NCHW fp32 (feature maps returned by
  * SNDisc.forward, disc.py:38; gradients flowing back into them). */
 int wu_nhwc_to_nchw_f32(const void* x, int ldx, float* y_nchw, int N, int H, int W, int C, int dtype, void* stream);

@@ -155,6 +155,9 @@ SIGNATURES = {
     "wu_feature_stats_update": (I, [P, I, I, I, P, I, P, P, P]),
     "wu_kid_workspace_bytes": (SZ, [I, I]),
     "wu_kid_mmd": (I, [P, I, I, P, I, I, P, I, I, I, I, c_double, c_double, P, P, P, P]),
+    "wu_prdc_workspace_bytes": (SZ, [I, I, I, I]),
+    "wu_knn_radii": (I, [P, I, I, I, I, I, P, P, P]),
+    "wu_prdc_counts": (I, [P, I, I, P, P, I, I, P, I, P, P, P, P, P]),
     "wu_prof_begin": (I, [ctypes.c_uint, I]),
     "wu_prof_query": (I, [I, POINTER(c_int), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "wu_prof_end": (I, []),

@@ -14,6 +14,9 @@ moments into fp64 device accumulators (wu_feature_stats_update); ``finalize`` tu
 on the fp64 matrix cores), the metric to read on a few hundred images, where the covariance above is rank-deficient.  It needs the rows
 themselves: a ``.npz`` PATH must then hold ``features`` (``wu.kid.FeatureBank.save_npz``); ``mu`` / ``sigma`` are computed from the rows
 when the file lacks them.
+
+``--prdc`` adds improved precision / recall and density / coverage (wu.prdc: k-NN manifold membership on the same rows, PATH1 the real
+set), which tell a loss of diversity from a loss of fidelity; it needs ``features`` in a ``.npz`` PATH just as ``--kid`` does.
 """
 import argparse
 import os
@@ -203,19 +206,26 @@ def _inception_for(paths, weights, dims, precision):
 def calculate_fid_and_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
                                       gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
     """(fid, (kid_mean, kid_std)) from ONE pass over each path: the feature rows feed the moment accumulators and a FeatureBank."""
-    from .kid import FeatureBank, kernel_inception_distance
+    from .kid import kernel_inception_distance
+    fid, banks = calculate_fid_and_banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy)
+    return fid, kernel_inception_distance(banks[0], banks[1], num_subsets=num_subsets, subset_size=subset_size, seed=seed)
+
+
+def calculate_fid_and_banks_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                                        gpu_entropy=False):
+    """(fid, (bank1, bank2)) from ONE pass over each path: the feature rows feed the moment accumulators and a FeatureBank each, which
+    wu.kid.kernel_inception_distance and wu.prdc.precision_recall_density_coverage then share (``--kid`` / ``--prdc``)."""
+    from .kid import FeatureBank
     model = _inception_for(paths, weights, dims, precision)
     banks = FeatureBank(), FeatureBank()
     m1, s1 = statistics_of_path(paths[0], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=banks[0])
     m2, s2 = statistics_of_path(paths[1], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=banks[1])
-    kid = kernel_inception_distance(banks[0], banks[1], num_subsets=num_subsets, subset_size=subset_size, seed=seed)
-    return calculate_frechet_distance(m1, s1, m2, s2), kid
+    return calculate_frechet_distance(m1, s1, m2, s2), banks
 
 
-def calculate_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                              gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
-    """(mean, std) of the Kernel Inception Distance between two image directories / .npz files holding ``features``."""
-    from .kid import FeatureBank, kernel_inception_distance
+def _banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy):
+    """The two paths' feature rows alone (no FID): a .npz needs ``features`` and nothing else."""
+    from .kid import FeatureBank
     model = _inception_for(paths, weights, dims, precision)
     banks = FeatureBank(), FeatureBank()
     for p, bank in zip(paths, banks):
@@ -223,7 +233,24 @@ def calculate_kid_given_paths(paths, weights, batch_size=50, dims=2048, precisio
             bank.append(FeatureBank.load_npz(p).features)
         else:
             statistics_of_path(p, model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=bank)
+    return banks
+
+
+def calculate_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                              gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
+    """(mean, std) of the Kernel Inception Distance between two image directories / .npz files holding ``features``."""
+    from .kid import kernel_inception_distance
+    banks = _banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy)
     return kernel_inception_distance(banks[0], banks[1], num_subsets=num_subsets, subset_size=subset_size, seed=seed)
+
+
+def calculate_prdc_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                               gpu_entropy=False, k=5):
+    """wu.prdc.PRDC(precision, recall, density, coverage) of paths[1] (the generated set) against paths[0] (the real set): two image
+    directories / .npz files holding ``features``, one pass over each."""
+    from .prdc import precision_recall_density_coverage
+    banks = _banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy)
+    return precision_recall_density_coverage(banks[0], banks[1], k=k)
 
 
 def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
@@ -261,7 +288,24 @@ def main(argv=None):
     ap.add_argument("--kid-subset-size", type=int, default=1000,
                     help="with --kid: rows per subset; an error, never clamped, when either path has fewer images")
     ap.add_argument("--kid-seed", type=int, default=2020, help="with --kid: seed of the subset draw (numpy RandomState)")
+    ap.add_argument("--prdc", action="store_true",
+                    help="also print improved precision / recall and density / coverage of the second path against the first (the real "
+                         "set); a .npz path must then hold 'features'")
+    ap.add_argument("--prdc-k", type=int, default=5, help="with --prdc: the k of the k-NN radii (prdc's default 5; Kynkaanniemi et al. use 3)")
     args = ap.parse_args(argv)
+    if args.prdc:
+        from .prdc import precision_recall_density_coverage
+        fid, banks = calculate_fid_and_banks_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode,
+                                                         args.gpu_decode_png, args.gpu_entropy)
+        print(f"FID: {fid}")
+        if args.kid:
+            from .kid import kernel_inception_distance
+            kid_mean, kid_std = kernel_inception_distance(banks[0], banks[1], num_subsets=args.kid_subsets, subset_size=args.kid_subset_size,
+                                                          seed=args.kid_seed)
+            print(f"KID: {kid_mean} \u00b1 {kid_std}")
+        m = precision_recall_density_coverage(banks[0], banks[1], k=args.prdc_k)
+        print(f"PRDC: precision {m.precision} recall {m.recall} density {m.density} coverage {m.coverage}")
+        return 0
     if args.kid:
         fid, (kid_mean, kid_std) = calculate_fid_and_kid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision,
                                                                      args.gpu_decode, args.gpu_decode_png, args.gpu_entropy,
