@@ -16,18 +16,11 @@ import pytest
 import torch
 
 import _prdc_ref as R
+from _padded_rows import padded as _padded
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NAN = float("nan")
-
-
-def _padded(a, ld, rows_after):
-    """The rows of `a` as a view of a wider, longer device buffer: padding columns and the rows after n hold NaN."""
-    n, d = a.shape
-    buf = torch.full((n + rows_after, ld), NAN, dtype=torch.float32, device=DEV)
-    buf[:n, :d] = torch.from_numpy(a).to(DEV)
-    return buf[:n, :d]
 
 
 @functools.lru_cache(maxsize=None)

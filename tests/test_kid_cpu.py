@@ -60,7 +60,8 @@ def test_subset_size_errors(n1, n2, m):
 
 def test_kernel_inception_distance_refuses_host_rows_and_oversized_subsets():
     import torch
-    from wu import kid
+    from wu import features, kid
+    assert kid.FeatureBank is features.FeatureBank                 # one class under its documented name and its new home
     with pytest.raises(ValueError, match="CUDA"):
         kid.kernel_inception_distance(torch.zeros(4, 3), torch.zeros(4, 3), subset_size=2)        # no host fallback
     with pytest.raises(ValueError, match="CUDA"):

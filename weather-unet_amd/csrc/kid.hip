@@ -1,34 +1,21 @@
 // Kernel Inception Distance: the unbiased polynomial-kernel MMD^2 of S random subsets of two feature banks, two launches in all.
 //   * kid_gram_kernel    one 64 x 64 tile of a subset's xx / yy / xy kernel matrix per workgroup: rows gathered through the index array,
-//                        widened to fp64 while staged through LDS, <x_i, y_j> on the fp64 matrix cores (v_mfma_f64_16x16x4_f64), and the
+//                        <x_i, y_j> on the fp64 matrix cores (gram_f64.h: the tile, its LDS staging and its fragment maps), and the
 //                        epilogue k = (gamma g + coef0)^degree summed to ONE double per tile -- the kernel matrix is never stored;
 //   * kid_finish_kernel  one wave per subset: the tiles' partial sums per block in tile order, then mmd2.
 // No atomics anywhere and every reduction in a fixed order: two runs give the same bits.
-#include "wu_common.h"
+#include "gram_f64.h"
 
 // the epilogue and mmd2 round every product and sum on its own, as the numpy restatement (tests/_kid_ref.py) does: no fused multiply-add
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef double f64x4_t __attribute__((ext_vector_type(4)));
-
-constexpr int kKidTile = 64;          // rows / columns of a workgroup's tile
-constexpr int kKidKC = 32;            // features per staged chunk
-constexpr int kKidLd = kKidKC + 1;    // LDS row stride in doubles: rows 8 bytes apart in bank space
-
-__host__ __device__ inline int kid_tiles_side(int m) { return (m + kKidTile - 1) / kKidTile; }
+__host__ __device__ inline int kid_tiles_side(int m) { return (m + kGramTile - 1) / kGramTile; }
 __host__ __device__ inline long long kid_tiles_tri(int T) { return (long long)T * (T + 1) / 2; }
 __host__ __device__ inline long long kid_tiles(int m) {
     const int T = kid_tiles_side(m);
     return 2 * kid_tiles_tri(T) + (long long)T * T;
-}
-
-// wave-level sum in a fixed order (lane l takes lane l + off, off = 32 .. 1); the total lands in lane 0
-__device__ __forceinline__ double kid_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
 }
 
 // grid (tiles, S).  Tile order inside a subset: the upper-triangular tiles of xx row by row ((0,0), (0,1), .. (0,T-1), (1,1), ..), the same
@@ -36,8 +23,8 @@ __device__ __forceinline__ double kid_wave_sum(double v) {
 __global__ __launch_bounds__(256) void kid_gram_kernel(const float* __restrict__ x, int ldx, int n1, const float* __restrict__ y, int ldy, int n2,
                                                        const int* __restrict__ idx, int m, int D, int degree, double gamma, double coef0,
                                                        double* __restrict__ partial) {
-    __shared__ double sP[kKidTile * kKidLd];      // tile rows   [row][k]
-    __shared__ double sQ[kKidTile * kKidLd];      // tile columns [row][k]
+    __shared__ double sP[kGramTile * kGramLd];    // tile rows   [row][k]
+    __shared__ double sQ[kGramTile * kGramLd];    // tile columns [row][k]
     __shared__ double sRed[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = blockIdx.y;
@@ -68,66 +55,15 @@ __global__ __launch_bounds__(256) void kid_gram_kernel(const float* __restrict__
     const int* pidx = idx + ((size_t)s * 2 + (block == 1 ? 1 : 0)) * m;
     const int* qidx = idx + ((size_t)s * 2 + (block == 0 ? 0 : 1)) * m;
 
-    // staging: thread -> feature k = tid & 31 of rows (tid >> 5) + 8 e, e = 0..7, of the tile rows and of the tile columns.  Positions past m
-    // read the subset's last row (their entries are zeroed below); indices are clamped into the bank, so nothing reads out of bounds.
-    const int sk = tid & 31, sr = tid >> 5;
-    const float* prow[8];
-    const float* qrow[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int r = sr + 8 * e;
-        const int pi = min(max(pidx[min(ti * kKidTile + r, m - 1)], 0), pn - 1);
-        const int qi = min(max(qidx[min(tj * kKidTile + r, m - 1)], 0), qn - 1);
-        prow[e] = pbase + (size_t)pi * pld;
-        qrow[e] = qbase + (size_t)qi * qld;
-    }
-    float pv[8], qv[8];
-    auto fetch = [&](int k0) {
-        const int k = k0 + sk;
-        const bool ok = k < D;                     // zero-filled tail of the last chunk
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            pv[e] = ok ? prow[e][k] : 0.f;
-            qv[e] = ok ? qrow[e][k] : 0.f;
-        }
-    };
+    // the tile's inner products (gram_f64.h).  Positions past m read the subset's last row (their entries are zeroed below); indices are
+    // clamped into the bank, so nothing reads out of bounds.
+    f64x4_t acc[2][2];
+    gram_tile_f64([&](int r) { return pbase + (size_t)min(max(pidx[min(ti * kGramTile + r, m - 1)], 0), pn - 1) * pld; },
+                  [&](int r) { return qbase + (size_t)min(max(qidx[min(tj * kGramTile + r, m - 1)], 0), qn - 1) * qld; }, D, sP, sQ, acc);
 
-    // each wave owns a 32 x 32 sub-tile: 2 x 2 accumulators of 16 x 16.  A = P[i = lane & 15][k], B = Q[j = lane & 15][k], one f64 per lane,
-    // lane group g = lane >> 4 taking one k of every four.  WHICH k a group takes only has to agree between A and B: group g reads
-    // k = 16 (g & 1) + 8 (g >> 1) + step, so the two groups of a half-wave sit 128 bytes apart in LDS and do not share banks.
+    // epilogue, on gram_f64.h's C/D map
     const int l15 = lane & 15, g = lane >> 4;
     const int wr = 32 * (wave >> 1), wc = 32 * (wave & 1);
-    const int kg = 16 * (g & 1) + 8 * (g >> 1);
-    const double* aP = sP + (wr + l15) * kKidLd + kg;
-    const double* bQ = sQ + (wc + l15) * kKidLd + kg;
-    f64x4_t acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = f64x4_t{0.0, 0.0, 0.0, 0.0};
-
-    fetch(0);
-    for (int k0 = 0; k0 < D; k0 += kKidKC) {
-        __syncthreads();                           // the previous chunk has been consumed
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            sP[(sr + 8 * e) * kKidLd + sk] = (double)pv[e];
-            sQ[(sr + 8 * e) * kKidLd + sk] = (double)qv[e];
-        }
-        __syncthreads();
-        if (k0 + kKidKC < D) fetch(k0 + kKidKC);   // the next chunk's loads fly under this chunk's MFMAs
-#pragma unroll
-        for (int st = 0; st < 8; ++st) {
-            const double a0 = aP[st], a1 = aP[16 * kKidLd + st];
-            const double b0 = bQ[st], b1 = bQ[16 * kKidLd + st];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-
-    // epilogue.  f64 C/D map: column = lane & 15, row = (lane >> 4) + 4 reg.
     const bool diag = block < 2 && ti == tj;
     double sum = 0.0;
 #pragma unroll
@@ -136,8 +72,8 @@ __global__ __launch_bounds__(256) void kid_gram_kernel(const float* __restrict__
         for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int gi = ti * kKidTile + wr + 16 * a + g + 4 * r;
-                const int gj = tj * kKidTile + wc + 16 * b + l15;
+                const int gi = ti * kGramTile + wr + 16 * a + g + 4 * r;
+                const int gj = tj * kGramTile + wc + 16 * b + l15;
                 const double tt = acc[a][b][r] * gamma + coef0;
                 double kv = tt;
                 for (int p = 1; p < degree; ++p) kv *= tt;
@@ -145,13 +81,13 @@ __global__ __launch_bounds__(256) void kid_gram_kernel(const float* __restrict__
                 sum += keep ? kv : 0.0;
             }
     if (block < 2 && ti < tj) sum *= 2.0;          // a strictly-upper tile stands for its mirror image too
-    sum = kid_wave_sum(sum);
+    sum = wave_sum_f64(sum);
     if (lane == 0) sRed[wave] = sum;
     __syncthreads();
     if (tid == 0) partial[(size_t)s * gridDim.x + blockIdx.x] = ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
 }
 
-// one wave per subset: lane l adds tiles l, l + 64, .. of a block in that order, the lanes are then summed in kid_wave_sum's order
+// one wave per subset: lane l adds tiles l, l + 64, .. of a block in that order, the lanes are then summed in wave_sum_f64's order
 __global__ __launch_bounds__(64) void kid_finish_kernel(const double* __restrict__ partial, int m, double* __restrict__ sums,
                                                         double* __restrict__ mmd2) {
     const int s = blockIdx.x, lane = threadIdx.x;
@@ -165,7 +101,7 @@ __global__ __launch_bounds__(64) void kid_finish_kernel(const double* __restrict
         const int lo = b * tri, hi = b == 2 ? ntiles : lo + tri;
         double acc = 0.0;
         for (int t = lo + lane; t < hi; t += 64) acc += p[t];
-        v[b] = kid_wave_sum(acc);
+        v[b] = wave_sum_f64(acc);
     }
     if (lane == 0) {
         const double sxx = v[0], syy = v[1], sxy = v[2];

@@ -2,7 +2,7 @@
 // manifold-membership counts from 64 x 64 tiles of squared distances that are never stored.
 //   * prdc_norms_kernel    |a|^2 of every row in fp64, one wave per row, a fixed order;
 //   * prdc_radii_kernel    grid (row tiles, column splits): a workgroup walks the column tiles of its split, <x_i, x_j> on the fp64 matrix
-//                          cores (v_mfma_f64_16x16x4_f64, rows widened to fp64 while staged through LDS, as kid_gram_kernel does),
+//                          cores (gram_f64.h: the tile kid_gram_kernel uses too, its LDS staging, fragment maps and barrier contract),
 //                          d^2 = max((|a|^2 + |b|^2) - 2 g, 0) handed through LDS to one thread per row, which keeps the row's k + 1
 //                          smallest in a sorted LDS list;
 //   * prdc_radii_finish    one thread per row merges the splits' lists; radius = the (k + 1)-th smallest;
@@ -11,26 +11,21 @@
 //                          integer adds.
 // Every sum that crosses a workgroup is an integer (vector integer atomics) and a radius is the k-th smallest of a multiset, so the same
 // inputs give the same bits whatever the arrival order.
-#include "wu_common.h"
+#include "gram_f64.h"
 
 // d^2 rounds every product and sum on its own, as the numpy restatement (tests/_prdc_ref.py) does: no fused multiply-add
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef double f64x4_t __attribute__((ext_vector_type(4)));
-
-constexpr int kTile = 64;             // rows / columns of a workgroup's tile
-constexpr int kKC = 32;               // features per staged chunk
-constexpr int kLd = kKC + 1;          // LDS row stride of a staged chunk in doubles
-constexpr int kTileLd = kTile + 1;    // LDS row stride of a d^2 tile: 64 x 65 doubles fit in the two staging buffers (2 x 64 x 33)
+constexpr int kDistLd = kGramTile + 1;    // LDS row stride of a d^2 tile: 64 x 65 doubles fit in the two staging buffers (2 x 64 x 33)
 constexpr int kMaxK = 16;             // largest k
 constexpr int kListLd = kMaxK + 1;    // a row's list: k + 1 <= 17 doubles
 constexpr int kMaxN = 1 << 21;        // rows per bank: row tiles fit grid.x, n (k + 1) splits stays far below 2^63
 constexpr int kMaxSplits = 1024;      // forced column splits (grid.y)
 constexpr int kTargetWorkgroups = 512;    // two per compute unit of a 256-CU part: what col_splits = 0 aims for
 
-__host__ __device__ inline int prdc_tiles(int n) { return (n + kTile - 1) / kTile; }
+__host__ __device__ inline int prdc_tiles(int n) { return (n + kGramTile - 1) / kGramTile; }
 
 // col_splits = 0: as many splits as it takes to reach kTargetWorkgroups, at most one per column tile
 inline int prdc_splits(int rows, int cols, int col_splits) {
@@ -40,14 +35,7 @@ inline int prdc_splits(int rows, int cols, int col_splits) {
     return s < 1 ? 1 : (s > tc ? tc : s);
 }
 
-// wave-level sum in a fixed order (lane l takes lane l + off, off = 32 .. 1); the total lands in lane 0
-__device__ __forceinline__ double prdc_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// one wave per row: lane l adds the squares of features l, l + 64, .. in that order, then the lanes in prdc_wave_sum's order
+// one wave per row: lane l adds the squares of features l, l + 64, .. in that order, then the lanes in wave_sum_f64's order
 __global__ __launch_bounds__(256) void prdc_norms_kernel(const float* __restrict__ x, int ldx, int n, int D, double* __restrict__ norms) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -58,7 +46,7 @@ __global__ __launch_bounds__(256) void prdc_norms_kernel(const float* __restrict
         const double v = (double)p[d];
         s += v * v;
     }
-    s = prdc_wave_sum(s);
+    s = wave_sum_f64(s);
     if (lane == 0) norms[row] = s;
 }
 
@@ -72,63 +60,12 @@ __global__ __launch_bounds__(256) void prdc_zero_kernel(unsigned* __restrict__ A
     if (i < n2) C[i] = 0u;
 }
 
-// <p_i, q_j> of tile (ti, tj) into the calling wave's 32 x 32 sub-tile: kid_gram_kernel's staging and fragment maps.  Thread -> feature
-// k = tid & 31 of rows (tid >> 5) + 8 e of the tile rows and of the tile columns; positions past pn / qn read the bank's last row (the callers
-// mask their entries), so nothing reads out of bounds; the tail of the last chunk is zero-filled.  A = P[i = lane & 15][k],
-// B = Q[j = lane & 15][k], lane group g = lane >> 4 reading k = 16 (g & 1) + 8 (g >> 1) + step.  Every chunk starts with a barrier, so the
-// caller may have used sP / sQ for something else before the call; it must place a barrier of its own before it reuses them after it.
+// <p_i, q_j> of tile (ti, tj) of two banks into the calling wave's acc (gram_f64.h, its barrier contract included).  Positions past pn / qn
+// read the bank's last row (the callers mask their entries), so nothing reads out of bounds.
 __device__ __forceinline__ void prdc_gram_tile(const float* __restrict__ p, int pld, int pn, int ti, const float* __restrict__ q, int qld, int qn,
                                                int tj, int D, double* sP, double* sQ, f64x4_t (&acc)[2][2]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int sk = tid & 31, sr = tid >> 5;
-    const float* prow[8];
-    const float* qrow[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int r = sr + 8 * e;
-        prow[e] = p + (size_t)min(ti * kTile + r, pn - 1) * pld;
-        qrow[e] = q + (size_t)min(tj * kTile + r, qn - 1) * qld;
-    }
-    float pv[8], qv[8];
-    auto fetch = [&](int k0) {
-        const int k = k0 + sk;
-        const bool ok = k < D;                     // zero-filled tail of the last chunk
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            pv[e] = ok ? prow[e][k] : 0.f;
-            qv[e] = ok ? qrow[e][k] : 0.f;
-        }
-    };
-    const int l15 = lane & 15, g = lane >> 4;
-    const int wr = 32 * (wave >> 1), wc = 32 * (wave & 1);
-    const int kg = 16 * (g & 1) + 8 * (g >> 1);
-    const double* aP = sP + (wr + l15) * kLd + kg;
-    const double* bQ = sQ + (wc + l15) * kLd + kg;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = f64x4_t{0.0, 0.0, 0.0, 0.0};
-
-    fetch(0);
-    for (int k0 = 0; k0 < D; k0 += kKC) {
-        __syncthreads();                           // the previous chunk (or the caller's use of the buffers) has been consumed
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            sP[(sr + 8 * e) * kLd + sk] = (double)pv[e];
-            sQ[(sr + 8 * e) * kLd + sk] = (double)qv[e];
-        }
-        __syncthreads();
-        if (k0 + kKC < D) fetch(k0 + kKC);         // the next chunk's loads fly under this chunk's MFMAs
-#pragma unroll
-        for (int st = 0; st < 8; ++st) {
-            const double a0 = aP[st], a1 = aP[16 * kLd + st];
-            const double b0 = bQ[st], b1 = bQ[16 * kLd + st];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
+    gram_tile_f64([&](int r) { return p + (size_t)min(ti * kGramTile + r, pn - 1) * pld; },
+                  [&](int r) { return q + (size_t)min(tj * kGramTile + r, qn - 1) * qld; }, D, sP, sQ, acc);
 }
 
 __device__ __forceinline__ double prdc_dist2(double na, double nb, double g) {
@@ -140,12 +77,12 @@ __device__ __forceinline__ double prdc_dist2(double na, double nb, double g) {
 // measured 5 % faster at n = 60 000 than the two the compiler settles on by itself (profiles/prdc_bench.md).
 __global__ __launch_bounds__(256, 3) void prdc_radii_kernel(const float* __restrict__ x, int ldx, int n, int D, int k,
                                                             const double* __restrict__ norms, double* __restrict__ lists) {
-    __shared__ double sStage[2 * kTile * kLd];     // the staged chunks; between two tiles the d^2 tile [row][column], stride kTileLd
-    __shared__ double sTop[kTile * kListLd];       // per tile row the k + 1 smallest d^2 so far, ascending
-    __shared__ double sNr[kTile];
-    static_assert(kTile * kTileLd <= 2 * kTile * kLd, "the d^2 tile must fit in the staging buffers");
+    __shared__ double sStage[2 * kGramTile * kGramLd];     // the staged chunks; between two tiles the d^2 tile [row][column], stride kDistLd
+    __shared__ double sTop[kGramTile * kListLd];           // per tile row the k + 1 smallest d^2 so far, ascending
+    __shared__ double sNr[kGramTile];
+    static_assert(kGramTile * kDistLd <= 2 * kGramTile * kGramLd, "the d^2 tile must fit in the staging buffers");
     double* sP = sStage;
-    double* sQ = sStage + kTile * kLd;
+    double* sQ = sStage + kGramTile * kGramLd;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const int wr = 32 * (wave >> 1), wc = 32 * (wave & 1);
@@ -156,9 +93,9 @@ __global__ __launch_bounds__(256, 3) void prdc_radii_kernel(const float* __restr
     const double inf = __builtin_huge_val();
 
     // threads 0..63 own one tile row's list each, from here to the end: no other thread touches sTop
-    if (tid < kTile) {
+    if (tid < kGramTile) {
         for (int j = 0; j <= k; ++j) sTop[tid * kListLd + j] = inf;
-        sNr[tid] = norms[min(ti * kTile + tid, n - 1)];    // |x_i|^2 of the tile rows: read behind the first tile's barriers
+        sNr[tid] = norms[min(ti * kGramTile + tid, n - 1)];    // |x_i|^2 of the tile rows: read behind the first tile's barriers
     }
 
     for (int tj = t0; tj < t1; ++tj) {
@@ -167,25 +104,25 @@ __global__ __launch_bounds__(256, 3) void prdc_radii_kernel(const float* __restr
         __syncthreads();                           // every wave is done with the staged chunks
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const int cj = wc + 16 * b + l15, gj = tj * kTile + cj;
+            const int cj = wc + 16 * b + l15, gj = tj * kGramTile + cj;
             const double nc = norms[min(gj, n - 1)];
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int ri = wr + 16 * a + g + 4 * r, gi = ti * kTile + ri;
-                    double d = prdc_dist2(sNr[ri], nc, acc[a][b][r]);      // C/D map: row = (lane >> 4) + 4 reg
+                    const int ri = wr + 16 * a + g + 4 * r, gi = ti * kGramTile + ri;
+                    double d = prdc_dist2(sNr[ri], nc, acc[a][b][r]);      // rows by gram_f64.h's C/D map
                     d = gi == gj ? 0.0 : d;        // the row itself: exactly 0
                     d = gj < n ? d : inf;          // columns past n count as +inf
-                    sStage[ri * kTileLd + cj] = d;
+                    sStage[ri * kDistLd + cj] = d;
                 }
         }
         __syncthreads();
-        if (tid < kTile) {
+        if (tid < kGramTile) {
             double* L = sTop + tid * kListLd;
-            const double* row = sStage + tid * kTileLd;
+            const double* row = sStage + tid * kDistLd;
             double worst = L[k];
-            for (int c = 0; c < kTile; ++c) {
+            for (int c = 0; c < kGramTile; ++c) {
                 const double v = row[c];
                 if (v < worst) {                   // a tie with the (k + 1)-th smallest leaves the (k + 1)-th smallest as it is
                     int j = k;
@@ -200,8 +137,8 @@ __global__ __launch_bounds__(256, 3) void prdc_radii_kernel(const float* __restr
         }
         // the next tile's first barrier (prdc_gram_tile) keeps the staging stores behind this scan
     }
-    const int gi = ti * kTile + tid;
-    if (tid < kTile && gi < n) {
+    const int gi = ti * kGramTile + tid;
+    if (tid < kGramTile && gi < n) {
         double* out = lists + ((size_t)gi * S + split) * (size_t)(k + 1);
         for (int j = 0; j <= k; ++j) out[j] = sTop[tid * kListLd + j];
     }
@@ -238,11 +175,11 @@ __global__ __launch_bounds__(256, 3) void prdc_counts_kernel(const float* __rest
                                                              const double* __restrict__ rx, const float* __restrict__ y, int ldy, int n2,
                                                              const double* __restrict__ ny, const double* __restrict__ ry, int D,
                                                              unsigned* __restrict__ A, unsigned* __restrict__ B, unsigned* __restrict__ C) {
-    __shared__ double sStage[2 * kTile * kLd];
-    __shared__ unsigned sA[kTile], sB[kTile], sC[kTile];
-    __shared__ double sNr[kTile], sRr[kTile];
+    __shared__ double sStage[2 * kGramTile * kGramLd];
+    __shared__ unsigned sA[kGramTile], sB[kGramTile], sC[kGramTile];
+    __shared__ double sNr[kGramTile], sRr[kGramTile];
     double* sP = sStage;
-    double* sQ = sStage + kTile * kLd;
+    double* sQ = sStage + kGramTile * kGramLd;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const int wr = 32 * (wave >> 1), wc = 32 * (wave & 1);
@@ -252,9 +189,9 @@ __global__ __launch_bounds__(256, 3) void prdc_counts_kernel(const float* __rest
     const int t0 = split * per, t1 = min(T, t0 + per);
     if (t0 >= t1) return;                          // an empty split: uniform over the workgroup
 
-    if (tid < kTile) {                             // seen by all behind the first tile's barriers
+    if (tid < kGramTile) {                             // seen by all behind the first tile's barriers
         sA[tid] = sB[tid] = sC[tid] = 0u;
-        const int gi = ti * kTile + tid;
+        const int gi = ti * kGramTile + tid;
         sNr[tid] = nx[min(gi, n1 - 1)];            // |x_i|^2 and radius_X[i] of the tile rows; a row past n1 gets radius -1: no d^2
         sRr[tid] = gi < n1 ? rx[gi] : -1.0;        // (>= 0) lies within it
     }
@@ -266,7 +203,7 @@ __global__ __launch_bounds__(256, 3) void prdc_counts_kernel(const float* __rest
         bool cok[2];
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const int gj = tj * kTile + wc + 16 * b + l15;
+            const int gj = tj * kGramTile + wc + 16 * b + l15;
             cok[b] = gj < n2;
             nc[b] = ny[min(gj, n2 - 1)];
             rc[b] = cok[b] ? ry[gj] : -1.0;
@@ -276,9 +213,9 @@ __global__ __launch_bounds__(256, 3) void prdc_counts_kernel(const float* __rest
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int ri = wr + 16 * a + g + 4 * r;        // C/D map: row = (lane >> 4) + 4 reg
+                const int ri = wr + 16 * a + g + 4 * r;        // rows by gram_f64.h's C/D map
                 const double nr = sNr[ri], rr = sRr[ri];
-                const bool rok = ti * kTile + ri < n1;
+                const bool rok = ti * kGramTile + ri < n1;
                 unsigned packed = 0u;              // this row's A count in the low half, its B count in the high half
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
@@ -303,16 +240,16 @@ __global__ __launch_bounds__(256, 3) void prdc_counts_kernel(const float* __rest
             if (g == 0 && c != 0u) atomicAdd(&sC[wc + 16 * b + l15], c);
         }
         __syncthreads();
-        if (tid < kTile) {
+        if (tid < kGramTile) {
             const unsigned c = sC[tid];
             if (c != 0u) {                         // only columns below n2 can be non-zero
-                atomicAdd(&C[tj * kTile + tid], c);
+                atomicAdd(&C[tj * kGramTile + tid], c);
                 sC[tid] = 0u;                      // seen by all behind the next tile's barriers
             }
         }
     }
-    const int gi = ti * kTile + tid;
-    if (tid < kTile && gi < n1) {                  // the last tile's barrier lies before this
+    const int gi = ti * kGramTile + tid;
+    if (tid < kGramTile && gi < n1) {                  // the last tile's barrier lies before this
         if (sA[tid] != 0u) atomicAdd(&A[gi], sA[tid]);
         if (sB[tid] != 0u) atomicAdd(&B[gi], sB[tid]);
     }

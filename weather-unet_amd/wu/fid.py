@@ -12,7 +12,7 @@ moments into fp64 device accumulators (wu_feature_stats_update); ``finalize`` tu
 
 ``--kid`` adds the Kernel Inception Distance (wu.kid: the unbiased polynomial-kernel MMD^2 over random subsets of the same feature rows,
 on the fp64 matrix cores), the metric to read on a few hundred images, where the covariance above is rank-deficient.  It needs the rows
-themselves: a ``.npz`` PATH must then hold ``features`` (``wu.kid.FeatureBank.save_npz``); ``mu`` / ``sigma`` are computed from the rows
+themselves: a ``.npz`` PATH must then hold ``features`` (``wu.features.FeatureBank.save_npz``); ``mu`` / ``sigma`` are computed from the rows
 when the file lacks them.
 
 ``--prdc`` adds improved precision / recall and density / coverage (wu.prdc: k-NN manifold membership on the same rows, PATH1 the real
@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .features import FeatureBank, as_rows
 from .inception import InceptionV3, global_avgpool
 from .layout import precision_code, stream_ptr
 
@@ -43,7 +44,7 @@ class FIDStatistics:
         self._sum = self._cross = self._shift = None
 
     def update(self, images, value_range=(0, 1), features=None):
-        """``features``: a wu.kid.FeatureBank that also receives the batch's rows (for the KID)."""
+        """``features``: a wu.features.FeatureBank that also receives the batch's rows (for the KID)."""
         feat = self.model(images, value_range=value_range)[0]
         n, c, h, w = feat.shape
         if h * w != 1 or feat.dtype != torch.float32:
@@ -56,8 +57,7 @@ class FIDStatistics:
 
     def update_features(self, feats):
         """Add a batch of feature rows (B, D) float32 on the GPU."""
-        if not feats.is_cuda or feats.dtype != torch.float32 or feats.dim() != 2 or feats.stride(1) != 1:
-            raise ValueError("FIDStatistics.update_features: expected a (B, D) float32 CUDA tensor with unit column stride")
+        feats = as_rows(feats, "FIDStatistics.update_features")
         b, d = feats.shape
         first = self._sum is None
         if first:
@@ -144,7 +144,7 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png
     through wu.jpeg.GPUJpegDecoder instead of the per-file Pillow loop; gpu_decode_png: through wu.png.GPUPngDecoder, which inflates the
     segmented PNGs wu.png_enc writes on the GPU and hands every other file to Pillow -- the same uint8 batch, hence the same statistics.
     gpu_entropy (implies gpu_decode): the JPEG decoder also Huffman-decodes on the GPU (``entropy="device"``).  All off by default.
-    features: a wu.kid.FeatureBank that also receives every feature row (the KID's input); a .npz must then hold ``features``, and its
+    features: a wu.features.FeatureBank that also receives every feature row (the KID's input); a .npz must then hold ``features``, and its
     ``mu`` / ``sigma`` are taken from the file when it has them and computed from the rows when it does not."""
     gpu_decode = gpu_decode or gpu_entropy
     if path.endswith(".npz"):
@@ -180,7 +180,6 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png
 
 
 def _npz_statistics_and_features(path, features):
-    from .kid import FeatureBank
     bank = FeatureBank.load_npz(path)
     if bank.n:
         features.append(bank.features)
@@ -192,69 +191,11 @@ def _npz_statistics_and_features(path, features):
     return stats.finalize()
 
 
-def _inception_for(paths, weights, dims, precision):
-    for p in paths:
-        if not os.path.exists(p):
-            raise RuntimeError(f"Invalid path: {p}")
-    if all(p.endswith(".npz") for p in paths):
-        return None
-    model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], precision=precision)
-    model.load_state_dict(torch.load(weights, map_location="cpu"))
-    return model
-
-
-def calculate_fid_and_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                                      gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
-    """(fid, (kid_mean, kid_std)) from ONE pass over each path: the feature rows feed the moment accumulators and a FeatureBank."""
-    from .kid import kernel_inception_distance
-    fid, banks = calculate_fid_and_banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy)
-    return fid, kernel_inception_distance(banks[0], banks[1], num_subsets=num_subsets, subset_size=subset_size, seed=seed)
-
-
-def calculate_fid_and_banks_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                                        gpu_entropy=False):
-    """(fid, (bank1, bank2)) from ONE pass over each path: the feature rows feed the moment accumulators and a FeatureBank each, which
-    wu.kid.kernel_inception_distance and wu.prdc.precision_recall_density_coverage then share (``--kid`` / ``--prdc``)."""
-    from .kid import FeatureBank
-    model = _inception_for(paths, weights, dims, precision)
-    banks = FeatureBank(), FeatureBank()
-    m1, s1 = statistics_of_path(paths[0], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=banks[0])
-    m2, s2 = statistics_of_path(paths[1], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=banks[1])
-    return calculate_frechet_distance(m1, s1, m2, s2), banks
-
-
-def _banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy):
-    """The two paths' feature rows alone (no FID): a .npz needs ``features`` and nothing else."""
-    from .kid import FeatureBank
-    model = _inception_for(paths, weights, dims, precision)
-    banks = FeatureBank(), FeatureBank()
-    for p, bank in zip(paths, banks):
-        if p.endswith(".npz"):
-            bank.append(FeatureBank.load_npz(p).features)
-        else:
-            statistics_of_path(p, model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=bank)
-    return banks
-
-
-def calculate_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                              gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
-    """(mean, std) of the Kernel Inception Distance between two image directories / .npz files holding ``features``."""
-    from .kid import kernel_inception_distance
-    banks = _banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy)
-    return kernel_inception_distance(banks[0], banks[1], num_subsets=num_subsets, subset_size=subset_size, seed=seed)
-
-
-def calculate_prdc_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                               gpu_entropy=False, k=5):
-    """wu.prdc.PRDC(precision, recall, density, coverage) of paths[1] (the generated set) against paths[0] (the real set): two image
-    directories / .npz files holding ``features``, one pass over each."""
-    from .prdc import precision_recall_density_coverage
-    banks = _banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy)
-    return precision_recall_density_coverage(banks[0], banks[1], k=k)
-
-
-def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                              gpu_entropy=False):
+def _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid, rows):
+    """What every entry point below shares: the path check, the model loaded once (not at all for .npz files alone) and ONE pass over each
+    path.  Returns (stats, banks), a list per path each: (mu, sigma) when ``fid`` and a FeatureBank of the feature rows when ``rows``, None
+    otherwise.  Without ``rows`` a .npz is read for ``mu`` / ``sigma`` only; with ``rows`` it must hold ``features``, and without ``fid``
+    it needs nothing else."""
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError(f"Invalid path: {p}")
@@ -262,9 +203,56 @@ def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precisio
     if not all(p.endswith(".npz") for p in paths):
         model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], precision=precision)
         model.load_state_dict(torch.load(weights, map_location="cpu"))
-    m1, s1 = statistics_of_path(paths[0], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy)
-    m2, s2 = statistics_of_path(paths[1], model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy)
-    return calculate_frechet_distance(m1, s1, m2, s2)
+    stats, banks = [], []
+    for p in paths:
+        bank = FeatureBank() if rows else None
+        if rows and not fid and p.endswith(".npz"):
+            bank.append(FeatureBank.load_npz(p).features)
+            st = None
+        else:
+            st = statistics_of_path(p, model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=bank)
+        stats.append(st if fid else None)
+        banks.append(bank)
+    return stats, banks
+
+
+def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                              gpu_entropy=False):
+    stats, _ = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=True, rows=False)
+    return calculate_frechet_distance(*stats[0], *stats[1])
+
+
+def calculate_fid_and_banks_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                                        gpu_entropy=False):
+    """(fid, (bank1, bank2)) from ONE pass over each path: the feature rows feed the moment accumulators and a FeatureBank each, which
+    wu.kid.kernel_inception_distance and wu.prdc.precision_recall_density_coverage then share (``--kid`` / ``--prdc``)."""
+    stats, banks = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=True, rows=True)
+    return calculate_frechet_distance(*stats[0], *stats[1]), tuple(banks)
+
+
+def calculate_fid_and_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                                      gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
+    """(fid, (kid_mean, kid_std)) from ONE pass over each path."""
+    from .kid import kernel_inception_distance
+    fid, banks = calculate_fid_and_banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy)
+    return fid, kernel_inception_distance(*banks, num_subsets=num_subsets, subset_size=subset_size, seed=seed)
+
+
+def calculate_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                              gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
+    """(mean, std) of the Kernel Inception Distance between two image directories / .npz files holding ``features``."""
+    from .kid import kernel_inception_distance
+    _, banks = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=False, rows=True)
+    return kernel_inception_distance(*banks, num_subsets=num_subsets, subset_size=subset_size, seed=seed)
+
+
+def calculate_prdc_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
+                               gpu_entropy=False, k=5):
+    """wu.prdc.PRDC(precision, recall, density, coverage) of paths[1] (the generated set) against paths[0] (the real set): two image
+    directories / .npz files holding ``features``, one pass over each."""
+    from .prdc import precision_recall_density_coverage
+    _, banks = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=False, rows=True)
+    return precision_recall_density_coverage(*banks, k=k)
 
 
 def main(argv=None):
@@ -293,29 +281,17 @@ def main(argv=None):
                          "set); a .npz path must then hold 'features'")
     ap.add_argument("--prdc-k", type=int, default=5, help="with --prdc: the k of the k-NN radii (prdc's default 5; Kynkaanniemi et al. use 3)")
     args = ap.parse_args(argv)
+    stats, banks = _pass_over_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png,
+                                    args.gpu_entropy, fid=True, rows=args.kid or args.prdc)
+    print(f"FID: {calculate_frechet_distance(*stats[0], *stats[1])}")
+    if args.kid:
+        from .kid import kernel_inception_distance
+        kid_mean, kid_std = kernel_inception_distance(*banks, num_subsets=args.kid_subsets, subset_size=args.kid_subset_size, seed=args.kid_seed)
+        print(f"KID: {kid_mean} \u00b1 {kid_std}")
     if args.prdc:
         from .prdc import precision_recall_density_coverage
-        fid, banks = calculate_fid_and_banks_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode,
-                                                         args.gpu_decode_png, args.gpu_entropy)
-        print(f"FID: {fid}")
-        if args.kid:
-            from .kid import kernel_inception_distance
-            kid_mean, kid_std = kernel_inception_distance(banks[0], banks[1], num_subsets=args.kid_subsets, subset_size=args.kid_subset_size,
-                                                          seed=args.kid_seed)
-            print(f"KID: {kid_mean} \u00b1 {kid_std}")
-        m = precision_recall_density_coverage(banks[0], banks[1], k=args.prdc_k)
+        m = precision_recall_density_coverage(*banks, k=args.prdc_k)
         print(f"PRDC: precision {m.precision} recall {m.recall} density {m.density} coverage {m.coverage}")
-        return 0
-    if args.kid:
-        fid, (kid_mean, kid_std) = calculate_fid_and_kid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision,
-                                                                     args.gpu_decode, args.gpu_decode_png, args.gpu_entropy,
-                                                                     args.kid_subsets, args.kid_subset_size, args.kid_seed)
-        print(f"FID: {fid}")
-        print(f"KID: {kid_mean} \u00b1 {kid_std}")
-        return 0
-    fid = calculate_fid_given_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png,
-                                    args.gpu_entropy)
-    print(f"FID: {fid}")
     return 0
 
 

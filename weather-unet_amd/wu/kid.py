@@ -2,8 +2,8 @@
 averaged over random subsets.  Unlike the FID it needs no D x D covariance, so it is usable on a few hundred images (the 500-photograph
 test split), where the Frechet distance runs on a rank-deficient matrix.
 
-    bank1, bank2 = FeatureBank(), FeatureBank()
-    bank1.append(feats)                                  # (B, D) float32 CUDA rows, what FIDStatistics.update_features takes
+    bank1, bank2 = FeatureBank(), FeatureBank()          # wu.features.FeatureBank, importable from here too
+    bank1.append(feats)                               # (B, D) float32 CUDA rows, what FIDStatistics.update_features takes
     mean, std = kernel_inception_distance(bank1, bank2)  # 100 subsets of 1000 rows, k(x, y) = (<x, y> / D + 1)^3
 
 Semantics, in full.  ``rng = np.random.RandomState(seed)``; for every subset, ``rng.choice(n1, m, replace=False)`` and then
@@ -12,70 +12,14 @@ Per subset ``sxx = sum_{i != j} k(x_i, x_j)``, ``syy`` likewise, ``sxy = sum_{i,
 ``mmd2 = (sxx + syy) / (m (m - 1)) - 2 sxy / (m m)``; the result is ``(np.mean, np.std)`` of the subsets' mmd2.  A subset size over
 min(n1, n2) is an error, never clamped.
 
-All subsets run in two launches (wu_kid_mmd, csrc/kid.hip): the rows are gathered through the index array on the device and the kernel
-matrices are never stored.  There is no host fallback."""
+All subsets run in two launches (wu_kid_mmd, csrc/kid.hip on the fp64 tile of csrc/gram_f64.h): the rows are gathered through the index
+array on the device and the kernel matrices are never stored.  There is no host fallback."""
 import numpy as np
 import torch
 
 from . import _lib
+from .features import FeatureBank, as_rows  # noqa: F401  (wu.kid.FeatureBank is the documented name of the class)
 from .layout import stream_ptr
-
-
-def _check_rows(feats, who):
-    if not torch.is_tensor(feats) or not feats.is_cuda or feats.dtype != torch.float32 or feats.dim() != 2 or feats.stride(1) != 1:
-        raise ValueError(f"{who}: expected a (B, D) float32 CUDA tensor with unit column stride")
-
-
-class FeatureBank:
-    """Feature rows kept on the GPU, appended batch by batch.  ``features`` is the (n, D) view of the rows so far, ``n`` their number; the
-    device buffer doubles when it is full.  ``save_npz`` / ``load_npz`` use the key ``features`` (float32)."""
-
-    def __init__(self, dim=None):
-        self.dim = dim
-        self.n = 0
-        self._buf = None
-
-    def append(self, feats):
-        _check_rows(feats, "FeatureBank.append")
-        b, d = feats.shape
-        if self.dim is None:
-            self.dim = d
-        elif d != self.dim:
-            raise ValueError(f"FeatureBank: feature width {d} differs from the bank's {self.dim}")
-        if self._buf is None or self.n + b > self._buf.shape[0]:
-            cap = max(64, self.n + b, 2 * (0 if self._buf is None else self._buf.shape[0]))
-            buf = torch.empty(cap, d, dtype=torch.float32, device=feats.device)
-            if self.n:
-                buf[:self.n].copy_(self._buf[:self.n])
-            self._buf = buf
-        self._buf[self.n:self.n + b].copy_(feats)
-        self.n += b
-
-    @property
-    def capacity(self):
-        return 0 if self._buf is None else self._buf.shape[0]
-
-    @property
-    def features(self):
-        if self._buf is None:
-            raise ValueError("FeatureBank: no rows yet")
-        return self._buf[:self.n]
-
-    def save_npz(self, path):
-        np.savez(path, features=self.features.cpu().numpy())
-
-    @classmethod
-    def load_npz(cls, path, device="cuda"):
-        with np.load(path) as f:
-            if "features" not in f:
-                raise ValueError(f"{path}: no 'features' array (keys {sorted(f.keys())}); KID needs the feature rows, not mu / sigma")
-            a = np.ascontiguousarray(f["features"], dtype=np.float32)
-        if a.ndim != 2:
-            raise ValueError(f"{path}: 'features' has shape {a.shape}, expected (n, D)")
-        bank = cls(a.shape[1])
-        if a.shape[0]:
-            bank.append(torch.from_numpy(a).to(device))
-        return bank
 
 
 def _check_subset_size(n1, n2, m):
@@ -102,8 +46,7 @@ def polynomial_mmd_subsets(f1, f2, indices, degree=3, gamma=None, coef0=1.0):
     """The thin wrapper over wu_kid_mmd.  f1 (n1, D), f2 (n2, D): float32 CUDA rows with unit column stride (any row stride);
     indices: (S, 2, m) integers (numpy or tensor), [:, 0] into f1 and [:, 1] into f2, checked here on the host.  Returns
     (sums (S, 3) = (sxx, syy, sxy), mmd2 (S,)) as float64 CUDA tensors; nothing is synchronised."""
-    _check_rows(f1, "polynomial_mmd_subsets")
-    _check_rows(f2, "polynomial_mmd_subsets")
+    f1, f2 = as_rows(f1, "polynomial_mmd_subsets"), as_rows(f2, "polynomial_mmd_subsets")
     if f1.shape[1] != f2.shape[1] or f1.device != f2.device:
         raise ValueError(f"polynomial_mmd_subsets: feature widths {f1.shape[1]} / {f2.shape[1]} or devices differ")
     idx = indices.detach().cpu().numpy() if torch.is_tensor(indices) else np.asarray(indices)
@@ -132,16 +75,10 @@ def polynomial_mmd_subsets(f1, f2, indices, degree=3, gamma=None, coef0=1.0):
     return sums, mmd2
 
 
-def _rows(f):
-    return f.features if isinstance(f, FeatureBank) else f
-
-
 def kernel_inception_distance(f1, f2, num_subsets=100, subset_size=1000, degree=3, gamma=None, coef0=1.0, seed=2020):
     """(mean, std) of the unbiased polynomial MMD^2 over ``num_subsets`` random subsets of ``subset_size`` rows of f1 and f2 (FeatureBanks
     or (n, D) float32 CUDA tensors).  ValueError when subset_size exceeds min(n1, n2)."""
-    f1, f2 = _rows(f1), _rows(f2)
-    _check_rows(f1, "kernel_inception_distance")
-    _check_rows(f2, "kernel_inception_distance")
+    f1, f2 = as_rows(f1, "kernel_inception_distance"), as_rows(f2, "kernel_inception_distance")
     idx = subset_indices(f1.shape[0], f2.shape[0], num_subsets, subset_size, seed)
     _, mmd2 = polynomial_mmd_subsets(f1, f2, idx, degree, gamma, coef0)
     v = mmd2.cpu().numpy()

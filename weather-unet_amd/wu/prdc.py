@@ -3,7 +3,7 @@ features of the HIP InceptionV3.  FID, IS and KID each mix fidelity and diversit
 towards a prototype (precision and density stay, recall and coverage drop) from one that leaves its input untouched.  Like the KID they need
 no covariance, so they are usable on the 500-photograph test split.
 
-    real, fake = FeatureBank(), FeatureBank()                             # wu.kid.FeatureBank: rows kept on the GPU
+    real, fake = FeatureBank(), FeatureBank()                             # wu.features.FeatureBank: rows kept on the GPU
     p, r, d, c = precision_recall_density_coverage(real, fake, k=5)        # prdc's default k; Kynkaanniemi et al. use k = 3
 
 Semantics, in full (prdc's, stated on squared distances).  For float32 rows a, b widened to float64,
@@ -16,14 +16,14 @@ may give radius 0).  With X the real bank (n1 rows) and Y the fake bank (n2 rows
 
 1 <= k <= 16; a bank with fewer than k + 1 rows is an error, never clamped.
 
-The distance matrices are never stored (wu_knn_radii / wu_prdc_counts, csrc/prdc.hip: 64 x 64 tiles on the fp64 matrix cores, consumed by
-the epilogue).  There is no host fallback."""
+The distance matrices are never stored (wu_knn_radii / wu_prdc_counts, csrc/prdc.hip: 64 x 64 tiles on the fp64 matrix cores, the tile of
+csrc/gram_f64.h that the KID shares, consumed by the epilogue).  There is no host fallback."""
 import collections
 
 import torch
 
 from . import _lib
-from .kid import FeatureBank
+from .features import as_rows
 from .layout import stream_ptr
 
 MAX_K = 16
@@ -33,9 +33,7 @@ PRDC = collections.namedtuple("PRDC", ["precision", "recall", "density", "covera
 
 
 def _rows(f, who):
-    f = f.features if isinstance(f, FeatureBank) else f
-    if not torch.is_tensor(f) or not f.is_cuda or f.dtype != torch.float32 or f.dim() != 2 or f.stride(1) != 1:
-        raise ValueError(f"{who}: expected a FeatureBank or an (n, D) float32 CUDA tensor with unit column stride")
+    f = as_rows(f, who)
     if f.shape[1] < 1:
         raise ValueError(f"{who}: feature width {f.shape[1]} must be at least 1")
     return f
