@@ -777,6 +777,30 @@ int wu_knn_radii(const float* x, int ldx, int n, int D, int k, int col_splits, v
 int wu_prdc_counts(const float* x, int ldx, int n1, const double* radii_x, const float* y, int ldy, int n2, const double* radii_y, int D,
                    void* workspace, unsigned* A, unsigned* B, unsigned* C, void* stream);
 
+/* ---- Paired content preservation (wu/paired.py): SSIM / MS-SSIM means and error sums of x against R conditioned outputs y --------------
+ * x (B, C, H, W) with ELEMENT strides (xs_n, xs_c, xs_h, xs_w), y (R, B, C, H, W) with (ys_r, ys_n, ys_c, ys_h, ys_w); dtype WU_F32, WU_BF16
+ * or WU_SSIM_U8.  A value is widened to fp64 and mapped v * scale + shift; L is the data range, C1 = (K1 L)^2, C2 = (K2 L)^2.  `window` is a
+ * HOST array of k doubles (k odd, 3..11): it is copied into the kernels' argument struct, no device buffer.  All arithmetic in fp64, every
+ * operation rounded on its own (no FMA), the valid filter along H first and then along W, taps in ascending order:
+ *     mu_x = F(x), mxx = mu_x mu_x, myy, mxy likewise;  sx = F(x x) - mxx,  sy = F(y y) - myy,  sxy = F(x y) - mxy
+ *     cs = (2 sxy + C2) / ((sx + sy) + C2),   ssim = ((2 mxy + C1) / ((mxx + myy) + C1)) cs        over (H - k + 1) x (W - k + 1) positions
+ * levels = 1 or 5; between levels both images go through ((p00 + p01) + (p10 + p11)) * 0.25 with a zero row / column in FRONT of an odd
+ * dimension (size s -> s / 2 + s % 2); levels = 5 needs min(H, W) > 16 (k - 1).
+ *     ssim_mean, cs_mean (R, B, C, levels): the means of the two maps;   err (R, B, 2): sum (x - y)^2 and sum |x - y| over C H W values;
+ *     ssim_map: NULL, or (R, B, C, H - k + 1, W - k + 1) for the level-0 ssim entries.
+ * A workgroup owns a wu_ssim_tile_h() x wu_ssim_tile_w() output tile of one (n, c), filters x once and walks the R rows (where B C tiles
+ * is too small to fill the device, the rows are split over several workgroups instead); no filtered map reaches global memory.  At most 2 * levels launches whatever B, R, C; per-tile sums go to `workspace` (wu_ssim_workspace_bytes, with the
+ * pooled fp64 levels) and are folded in a fixed order: no atomics, the same inputs give the same bits, and a row's numbers do not depend
+ * on R.  Stream-ordered, caller-owned buffers, no allocation, no synchronisation. */
+#define WU_SSIM_U8 2
+size_t wu_ssim_workspace_bytes(int B, int R, int C, int H, int W, int k, int levels);      /* 0 for anything out of range */
+int wu_ssim_tile_h(void);
+int wu_ssim_tile_w(void);
+int wu_ssim_pairs(const void* x, long long xs_n, long long xs_c, long long xs_h, long long xs_w, const void* y, long long ys_r,
+                  long long ys_n, long long ys_c, long long ys_h, long long ys_w, int dtype, int B, int R, int C, int H, int W,
+                  double scale, double shift, double L, double K1, double K2, const double* window, int k, int levels,
+                  void* workspace, double* ssim_mean, double* cs_mean, double* err, double* ssim_map, void* stream);
+
 /* layout helpers for the module boundary: NHWC `dtype` <-> NCHW fp32 (feature maps returned by
  * SNDisc.forward, disc.py:38; gradients flowing back into them). */
 int wu_nhwc_to_nchw_f32(const void* x, int ldx, float* y_nchw, int N, int H, int W, int C, int dtype, void* stream);

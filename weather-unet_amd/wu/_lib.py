@@ -158,6 +158,10 @@ SIGNATURES = {
     "wu_prdc_workspace_bytes": (SZ, [I, I, I, I]),
     "wu_knn_radii": (I, [P, I, I, I, I, I, P, P, P]),
     "wu_prdc_counts": (I, [P, I, I, P, P, I, I, P, I, P, P, P, P, P]),
+    "wu_ssim_workspace_bytes": (SZ, [I, I, I, I, I, I, I]),
+    "wu_ssim_tile_h": (I, []),
+    "wu_ssim_tile_w": (I, []),
+    "wu_ssim_pairs": (I, [P] + [ctypes.c_longlong] * 4 + [P] + [ctypes.c_longlong] * 5 + [I] * 6 + [c_double] * 5 + [P, I, I, P, P, P, P, P, P]),
     "wu_prof_begin": (I, [ctypes.c_uint, I]),
     "wu_prof_query": (I, [I, POINTER(c_int), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "wu_prof_end": (I, []),

@@ -6,11 +6,13 @@
                                                                prediction minus the row, averaged per row: mean / std of those errors
 * ``ClassifierEval``         eval_classifier_i2w.py:85-106     the classifier on the photographs themselves (no generator)
 * ``EstimatorEval``          eval_estimator.py:141-159         the estimator on the photographs themselves: mean / std of pred - target, MSE
+* ``ContentPreservation``    (no counterpart in the reference) SSIM / MS-SSIM / MSE / PSNR / MAE between every image and its transferred versions,
+                                                               per row; the two transfer evaluations feed it through ``content=``
 
 No pandas, plotting or path conventions: callers feed batches (e.g. from ``wu.data.JpegBatchLoader``).  Every ``update`` accumulates on the
 device and never synchronises with the host; ``confusion`` / ``report`` / ``result`` read the accumulators back.  The generator and the
 networks run in whatever train / eval mode they are in (the reference's scripts leave the generator's Dropout active and call ``.eval()`` on
-the classifier / estimator).  Not a hot path: torch arithmetic on a few numbers per image, no kernel of its own.
+the classifier / estimator).  Not a hot path: torch arithmetic on a few numbers per image; the one kernel behind it is ``wu.paired``'s.
 """
 import torch
 
@@ -96,17 +98,52 @@ def _batched(net, images, max_images):
     return torch.cat([net(images[i:i + max_images]).float() for i in range(0, images.shape[0], max_images)])
 
 
+class ContentPreservation:
+    """Is it still the same scene?  The paired metrics of ``wu.paired`` (SSIM, MS-SSIM, MSE / PSNR, MAE) between a batch and its R conditioned
+    outputs, accumulated per row over a data set.  ``add(batch, fakes)``: batch (B, C, H, W), fakes (R, B, C, H, W) as ``sweep`` returns them
+    (R fixed across calls); one fused call per batch, sums kept in fp64 on the device, no host synchronisation.  ``result()``: per row (R,)
+    fp64 CPU tensors ``ssim``, ``ms_ssim`` (None with ms=False), ``mse``, ``mae`` -- means over all images -- ``psnr = 10 log10(L^2 / mean
+    MSE)`` and the image ``count``.  ms=True needs min(H, W) > 16 (win_size - 1): a ValueError otherwise, never a silent clamp."""
+
+    def __init__(self, ms=True, value_range=(-1, 1), win_size=11):
+        self.ms, self.value_range, self.win_size = bool(ms), value_range, int(win_size)
+        self.sums, self.count, self.data_range = None, 0, None
+
+    @torch.no_grad()
+    def add(self, batch, fakes):
+        from . import paired
+        if fakes.dim() != 5:
+            raise ValueError(f"ContentPreservation.add: fakes must be (R, B, C, H, W), got {tuple(fakes.shape)}")
+        st = paired.pair_stats(batch, fakes, self.value_range, self.win_size, levels=paired.MS_LEVELS if self.ms else 1)
+        cols = [paired.combine_ssim(st), paired.combine_ms_ssim(st) if self.ms else torch.zeros_like(st.err[..., 0]),
+                paired.mse_of(st), paired.mae_of(st)]
+        part = torch.stack(cols, -1).sum(1)                                   # (R, 4)
+        if self.sums is not None and self.sums.shape != part.shape:
+            raise ValueError(f"ContentPreservation.add: {part.shape[0]} rows after {self.sums.shape[0]}")
+        self.sums = part if self.sums is None else self.sums + part
+        self.count += batch.shape[0]
+        self.data_range = st.data_range
+
+    def result(self):
+        if self.sums is None:
+            raise RuntimeError("no batch has been added yet")
+        m = (self.sums / self.count).cpu()
+        return {"ssim": m[:, 0], "ms_ssim": m[:, 1] if self.ms else None, "mse": m[:, 2], "mae": m[:, 3],
+                "psnr": 10.0 * torch.log10(self.data_range * self.data_range / m[:, 2]), "count": self.count}
+
+
 class ClassTransferEval(_Confusion):
     """eval_class_transfer.py:106-136.  ``update(batch)`` transfers every image of the batch to every class (``transfer.sweep`` over the
     identity rows: the encoder runs once per batch), runs ``classifier`` over the nc * B outputs in passes of at most ``max_images`` images
     and counts arg-max of its fp32 logits (the script's Softmax does not move the arg-max) against the TARGET class.  The script's loop runs
     ``for i in range(bs)`` over ``onehot[i]``, i.e. it assumes batch size == number of classes; this one always covers all classes, like
     ``infer_driver.class_sweep``.  ``confusion()``: int64 (nc, nc), rows = target class, columns = predicted class; ``report()``:
-    ``classification_report`` of it.  With the generator's dropout active the masks are those of ``sweep`` (the repeated-batch forward)."""
+    ``classification_report`` of it.  With the generator's dropout active the masks are those of ``sweep`` (the repeated-batch forward).
+    ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per class."""
 
-    def __init__(self, transfer, classifier, num_classes, max_images=SWEEP_MAX_IMAGES, names=None):
+    def __init__(self, transfer, classifier, num_classes, max_images=SWEEP_MAX_IMAGES, names=None, content=None):
         super().__init__(num_classes, names)
-        self.transfer, self.classifier, self.max_images = transfer, classifier, int(max_images)
+        self.transfer, self.classifier, self.max_images, self.content = transfer, classifier, int(max_images), content
 
     @torch.no_grad()
     def update(self, batch):
@@ -114,16 +151,19 @@ class ClassTransferEval(_Confusion):
         fakes = self.transfer.sweep(batch, torch.eye(nc, device=batch.device), self.max_images)
         logits = _batched(self.classifier, fakes.view(nc * b, *batch.shape[1:]), self.max_images)
         self.add(torch.arange(nc, device=batch.device).repeat_interleave(b), logits.argmax(1))
+        if self.content is not None:
+            self.content.add(batch, fakes)
 
 
 class EstimatorTransferEval(_Rows):
     """eval_estimator_transfer.py:48-61,129-130.  ``update(batch, ref_signals)`` transfers every image of the batch to every row of
     ``ref_signals`` (R, nc) (``transfer.sweep``), runs ``estimator`` over the outputs and appends, per row, the batch mean of
-    ``pred - row`` (:54-57); ``result()``: fp64 ``mean`` and population ``std`` over all appended rows (:129-130) and their ``count``."""
+    ``pred - row`` (:54-57); ``result()``: fp64 ``mean`` and population ``std`` over all appended rows (:129-130) and their ``count``.
+    ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per reference row."""
 
-    def __init__(self, transfer, estimator, max_images=SWEEP_MAX_IMAGES):
+    def __init__(self, transfer, estimator, max_images=SWEEP_MAX_IMAGES, content=None):
         super().__init__()
-        self.transfer, self.estimator, self.max_images = transfer, estimator, int(max_images)
+        self.transfer, self.estimator, self.max_images, self.content = transfer, estimator, int(max_images), content
 
     @torch.no_grad()
     def update(self, batch, ref_signals):
@@ -132,6 +172,8 @@ class EstimatorTransferEval(_Rows):
         fakes = self.transfer.sweep(batch, ref, self.max_images)
         pred = _batched(self.estimator, fakes.view(r * b, *batch.shape[1:]), self.max_images).view(r, b, -1)
         self.add((pred - ref.unsqueeze(1)).mean(1))
+        if self.content is not None:
+            self.content.add(batch, fakes)
 
 
 class ClassifierEval(_Confusion):
