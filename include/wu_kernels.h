@@ -193,7 +193,9 @@ int wu_conv3x3_wgrad(const void* x, int ldx, const void* dy, int lddy, const voi
 
 /* Data gradient of the stride-2 conv (nets.py:30-31): dx (N,H,W,Cin) from dy (N,Ho,Wo,Cout),
  * w_dgrad as packed above; dy gated by act'(y) when y != NULL.  `workspace` holds
- * wu_conv3x3_s2_dgrad_workspace() bytes (the zero-upsampled gradient); egate as in wu_conv3x3_fwd. */
+ * wu_conv3x3_s2_dgrad_workspace() bytes (the zero-upsampled gradient); egate as in wu_conv3x3_fwd,
+ * except that a bf16 LeakyReLU gate multiplies the fp32 sum, in front of the ONE rounding, on every
+ * path (wu_conv3x3_fwd gates the stored bf16 value: the two roundings of a stand-alone gate pass). */
 size_t wu_conv3x3_s2_dgrad_workspace(int N, int H, int W, int Cout, int dtype);
 int wu_conv3x3_s2_dgrad(const void* dy, int lddy, const void* y, int ldy_, int act, const void* w_dgrad,
                         void* dx, int lddx, void* workspace, size_t workspace_bytes,

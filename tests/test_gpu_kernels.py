@@ -327,17 +327,19 @@ def test_adain_upcat_bwd_mask_bits_vs_rehash(p):
     res = []
     # both runs on the MARCHING kernel (option 8 = 5): the LDS-ring kernel of round 4 needs stored bits, and its per-(n, c) partial sums
     # are grouped by other tiles (tests/test_gpu_round4.py compares it with this one)
-    _lib.call("wu_set_option", 8, 5)
-    for mb in (bits.data_ptr(), None):
-        dx = empty_nhwc(n, c, h, w, _tdt(p), _dev())
-        dstd, dmean = torch.empty((n, c), device=_dev()), torch.empty((n, c), device=_dev())
-        gtmp = torch.empty((n, h, w, c), dtype=_tdt(p), device=_dev())
-        sums = torch.empty((n, c, 2 * (1 + WF.MAX_SPLITS)), device=_dev())
-        _lib.call("wu_adain_upcat_bwd", g.data_ptr(), nhwc_ld(g), x.data_ptr(), nhwc_ld(x), stats.data_ptr(), ystd.data_ptr(),
-                  dx.data_ptr(), nhwc_ld(dx), dstd.data_ptr(), dmean.data_ptr(), gtmp.data_ptr(), sums.data_ptr(),
-                  n, h, w, c, 0.3, seed, mb, 0, code, s)
-        res.append((dx.clone(), dstd.clone(), dmean.clone()))
-    _lib.call("wu_set_option", 8, 1)
+    try:
+        _lib.call("wu_set_option", 8, 5)
+        for mb in (bits.data_ptr(), None):
+            dx = empty_nhwc(n, c, h, w, _tdt(p), _dev())
+            dstd, dmean = torch.empty((n, c), device=_dev()), torch.empty((n, c), device=_dev())
+            gtmp = torch.empty((n, h, w, c), dtype=_tdt(p), device=_dev())
+            sums = torch.empty((n, c, 2 * (1 + WF.MAX_SPLITS)), device=_dev())
+            _lib.call("wu_adain_upcat_bwd", g.data_ptr(), nhwc_ld(g), x.data_ptr(), nhwc_ld(x), stats.data_ptr(), ystd.data_ptr(),
+                      dx.data_ptr(), nhwc_ld(dx), dstd.data_ptr(), dmean.data_ptr(), gtmp.data_ptr(), sums.data_ptr(),
+                      n, h, w, c, 0.3, seed, mb, 0, code, s)
+            res.append((dx.clone(), dstd.clone(), dmean.clone()))
+    finally:
+        _lib.call("wu_set_option", 8, 1)         # the process-global option is back at its default whatever happened
     for a, b in zip(*res):
         assert torch.equal(a, b)
 

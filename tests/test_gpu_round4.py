@@ -464,7 +464,14 @@ def test_stride2_conv_on_the_gathered_row_pipeline(shape):
             for o in outs:
                 assert (o - want).abs().max().item() <= 1.5e-2 * scale
             assert torch.equal(outs[1], outs[2]), "5 workgroups against the whole chip"
-            assert (outs[0] - outs[1]).abs().max().item() <= 8e-3 * scale, "gathered-row form against the register-staged kernel"
+            # On integers the two forms are bit-identical (tests/test_gpu_pointwise_exact.py::test_stride2_conv3x3_every_path_is_exact).  On
+            # these floats only the order of the fp32 sum differs: the two sums are at most d apart -- two runs of 9 Cin / 16 MFMA steps + the
+            # 9 tap folds, each rounding a partial sum of at most P = 9 Cin max|x| max|w| + max|b| to 2^-24 of it --, so the two bf16 results
+            # are the same value or neighbours (one ulp: 2^-7 of the larger at most), or below d themselves.
+            p_max = 9 * cin * 1.0 * 0.05 + 0.2
+            d = 2 * (9 * cin / 16 + 9) * 2.0 ** -24 * p_max
+            allowed = (2.0 ** -7 * torch.maximum(outs[0].abs(), outs[1].abs()) + d).clamp(max=8e-3 * scale)     # never more than the earlier bound
+            assert bool(((outs[0] - outs[1]).abs() <= allowed).all()), "gathered-row form against the register-staged kernel: more than one bf16 ulp + the fp32 order apart"
     finally:
         _lib.call("wu_set_option", OPT_PW3, DEFAULT)
         _lib.call("wu_set_option", OPT_GRID, 0)

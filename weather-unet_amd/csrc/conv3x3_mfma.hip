@@ -37,6 +37,10 @@ struct ConvArgs {
     void* y;
     const void* egate;
     int ldx, ldmask, ldy, ldegate, egate_act;
+    // 1: this launch belongs to the stride-2 data gradient (wu_conv3x3_s2_dgrad), whose LeakyReLU gate meets the fp32 value in front of the
+    // ONE rounding on every path (as the gathered-row form in resnet.hip).  0: the gate is applied to the stored value, the two roundings
+    // of a stand-alone gate pass (what wu/disc_graph.py relies on for the stride-1 data gradients).
+    int late_gate;
     int N, H, W, Ho, Wo, Cin, Cout;
     int act, mask_act;
     int tw_log2;      // tile width  = 1 << tw_log2  (output pixels)
@@ -259,7 +263,22 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 1) void conv3x3_mfma_kernel(
                     ElemTraits<T>::store((T*)(smem + row * kRow) + 32 * ni + l31, v);
                 }
     };
-    if (a.act == WU_ACT_RELU) epi_write(std::integral_constant<int, WU_ACT_RELU>{});
+    // ConvArgs::late_gate (bf16): the LeakyReLU gate multiplies by 0.2f in front of the ONE rounding.  That tile crosses LDS as fp32: 256 rows of
+    // 272 bytes, which launch_conv allocates for such a launch.
+    constexpr int kRow32 = kBN * 4 + 16;
+    const bool late_gate = sizeof(T) == 2 && a.late_gate != 0;
+    if (late_gate) {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int row = 64 * wave + 32 * mi + (i & 3) + 8 * (i >> 2) + 4 * lh;
+                    ((float*)(smem + row * kRow32))[32 * ni + l31] = act_apply(acc[mi][ni][i] + bv[ni], a.act);
+                }
+    }
+    else if (a.act == WU_ACT_RELU) epi_write(std::integral_constant<int, WU_ACT_RELU>{});
     else if (a.act == WU_ACT_LEAKY) epi_write(std::integral_constant<int, WU_ACT_LEAKY>{});
     else epi_write(std::integral_constant<int, WU_ACT_NONE>{});
     __syncthreads();
@@ -275,10 +294,22 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 1) void conv3x3_mfma_kernel(
         const int ph = SPARSE ? oh * a.osy + a.cls_ooy[cls] : oh, pw = SPARSE ? ow * a.osx + a.cls_oox[cls] : ow;
         const int PW = SPARSE ? a.OW : a.Wo;
         if (oh < a.Ho && ow < a.Wo && (!SPARSE || (ph < a.OH && pw < a.OW))) {
-            uint4 v = *(const uint4*)(smem + r * kRow + s * 16);
-            if (a.egate) {
-                const T* eg = (const T*)a.egate + ((size_t)n * OHW + (size_t)(ph * PW + pw)) * a.ldegate + co0 + s * (16 / (int)sizeof(T));
-                v = gate16<T>(v, *(const uint4*)eg, a.egate_act);
+            uint4 v;
+            if (late_gate) {
+                const T* eg = (const T*)a.egate + ((size_t)n * OHW + (size_t)(ph * PW + pw)) * a.ldegate + co0 + s * 8;
+                float f[8], e[8];
+                unpack16<float>(*(const uint4*)(smem + r * kRow32 + s * 32), f);
+                unpack16<float>(*(const uint4*)(smem + r * kRow32 + s * 32 + 16), f + 4);
+                unpack16<bf16_t>(*(const uint4*)eg, e);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) f[i] = act_gate(f[i], e[i], WU_ACT_LEAKY);
+                v = pack16<bf16_t>(f);
+            } else {
+                v = *(const uint4*)(smem + r * kRow + s * 16);
+                if (a.egate) {
+                    const T* eg = (const T*)a.egate + ((size_t)n * OHW + (size_t)(ph * PW + pw)) * a.ldegate + co0 + s * (16 / (int)sizeof(T));
+                    v = gate16<T>(v, *(const uint4*)eg, a.egate_act);
+                }
             }
             *(uint4*)(yout + (size_t)(ph * PW + pw) * a.ldy + s * (16 / (int)sizeof(T))) = v;
         }
@@ -294,6 +325,9 @@ int launch_conv(const ConvArgs& a, size_t lds_bytes, int grid, hipStream_t s) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
+    // a late-gated bf16 tile crosses LDS as fp32 (the kernel's epilogue): 256 rows of 272 bytes
+    const size_t late_gate_epi = (size_t)kTilePix * (kBN * 4 + 16);
+    if (sizeof(T) == 2 && a.late_gate && lds_bytes < late_gate_epi) lds_bytes = late_gate_epi;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, s, a);
     return 0;
 }
@@ -307,6 +341,7 @@ int conv_s2_dgrad_parity_launch(const void* dy, int lddy, const void* w_dgrad, v
     ConvArgs a;
     a.x = dy; a.mask = nullptr; a.w = w_dgrad; a.bias = nullptr; a.y = dx; a.egate = egate;
     a.ldx = lddy; a.ldmask = 0; a.ldy = lddx; a.ldegate = ldegate; a.egate_act = egate_act;
+    a.late_gate = (dtype == WU_BF16 && egate != nullptr && egate_act == WU_ACT_LEAKY) ? 1 : 0;
     a.N = N; a.H = Ho; a.W = Wo; a.Ho = Ho; a.Wo = Wo;
     a.Cin = Cout;                       // the GEMM's K: the forward conv's output channels
     a.Cout = Cin;                       // ... and its N: the forward conv's input channels
@@ -350,6 +385,15 @@ extern "C" int wu_conv3x3_fwd(const void* x, int ldx, const void* w_packed, cons
                               int N, int H, int W, int Cin, int Cout, int stride, int act,
                               const void* mask, int ldmask, int mask_act,
                               const void* egate, int ldegate, int egate_act, int dtype, void* stream) {
+    return conv3x3_fwd_dispatch(x, ldx, w_packed, bias, y, ldy, N, H, W, Cin, Cout, stride, act, mask, ldmask, mask_act, egate, ldegate, egate_act, 0, dtype, stream);
+}
+
+// wu_conv3x3_fwd, and (late_gate = 1) the stride-1 conv behind the zero-stuffed gradient of wu_conv3x3_s2_dgrad: a LeakyReLU gate in front of
+// the one rounding, which only the register-staged template below implements -- such a launch goes there whatever its shape
+int conv3x3_fwd_dispatch(const void* x, int ldx, const void* w_packed, const float* bias, void* y, int ldy,
+                         int N, int H, int W, int Cin, int Cout, int stride, int act,
+                         const void* mask, int ldmask, int mask_act,
+                         const void* egate, int ldegate, int egate_act, int late_gate, int dtype, void* stream) {
     const int esz = dtype == WU_BF16 ? 2 : 4;
     const int chunk = kChunkBytes / esz;
     WU_REQUIRE(dtype == WU_F32 || dtype == WU_BF16, "conv3x3_fwd: bad dtype %d", dtype);
@@ -366,6 +410,8 @@ extern "C" int wu_conv3x3_fwd(const void* x, int ldx, const void* w_packed, cons
     ConvArgs a;
     a.x = x; a.mask = mask; a.w = w_packed; a.bias = bias; a.y = y; a.egate = egate;
     a.ldx = ldx; a.ldmask = ldmask; a.ldy = ldy; a.ldegate = ldegate; a.egate_act = egate_act;
+    late_gate = (late_gate && dtype == WU_BF16 && egate != nullptr && egate_act == WU_ACT_LEAKY) ? 1 : 0;
+    a.late_gate = late_gate;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
     a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1;
     a.act = act; a.mask_act = mask_act;
@@ -385,7 +431,7 @@ extern "C" int wu_conv3x3_fwd(const void* x, int ldx, const void* w_packed, cons
     hipStream_t s = (hipStream_t)stream;
     const bool m = mask != nullptr;
     const int fam = stride == 2 ? WU_FAM_CONV_S2 : (m ? WU_FAM_CONV_DGRAD : WU_FAM_CONV_FWD);
-    if (g_wu_opt[WU_OPT_CONV_V2] && conv_v2_eligible(H, W, ldx, ldy, Cin, Cout, stride, dtype, m) && (egate == nullptr || (act == WU_ACT_NONE && bias == nullptr))) {
+    if (!late_gate && g_wu_opt[WU_OPT_CONV_V2] && conv_v2_eligible(H, W, ldx, ldy, Cin, Cout, stride, dtype, m) && (egate == nullptr || (act == WU_ACT_NONE && bias == nullptr))) {
         wu_prof_pre(fam, s);
         const int rc = conv_v2_launch(x, ldx, w_packed, bias, y, ldy, egate, ldegate, egate_act, N, H, W, Cin, Cout, act, s);
         WU_REQUIRE(rc == 0, "conv3x3_fwd: grid too large");
@@ -400,7 +446,7 @@ extern "C" int wu_conv3x3_fwd(const void* x, int ldx, const void* w_packed, cons
     //  against a halo in LDS -- and 512 -> 512 @8x8 48 against 68 only from batch 64: not taken)
     // Round 4 (later): small images on their own kernel -- on a 16x16 image the 256-pixel tile of the template below is the whole image (128 workgroups
     // at B = 32), on 8x8 three quarters of it lie outside
-    if (dtype == WU_BF16 && !m && stride == 1 && g_wu_opt[WU_OPT_CONV_SMALL] &&
+    if (!late_gate && dtype == WU_BF16 && !m && stride == 1 && g_wu_opt[WU_OPT_CONV_SMALL] &&
         conv_small_launch(x, ldx, w_packed, bias, y, ldy, egate, ldegate, egate_act, N, H, W, Cin, Cout, act, s) == 0) {
         const double pix = (double)N * H * W;
         wu_prof_post(fam, s, 2.0 * pix * Cout * 9.0 * Cin, (pix * (Cin + Cout) + 9.0 * Cin * Cout) * esz);

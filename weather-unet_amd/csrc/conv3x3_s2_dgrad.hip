@@ -71,6 +71,7 @@ extern "C" int wu_conv3x3_s2_dgrad(const void* dy, int lddy, const void* y, int 
         hipLaunchKernelGGL(upsample_zero_gate_kernel<float>, dim3((int)g), dim3(256), 0, s, (const float*)dy, lddy, (const float*)y, ldy_, act, (float*)workspace, N, H, W, Ho, Wo, Cout);
     WU_LAUNCH_CHECK("conv3x3_s2_dgrad(upsample)");
     // stride-1 correlation of the upsampled gradient with the rotated filter: channels swap roles
-    return wu_conv3x3_fwd(workspace, Cout, w_dgrad, nullptr, dx, lddx, N, H, W, /*Cin=*/Cout, /*Cout=*/Cin, 1, WU_ACT_NONE,
-                          nullptr, 0, 0, egate, ldegate, egate_act, dtype, stream);
+    // (late_gate: a LeakyReLU gate meets the fp32 sum, one rounding -- the same bits as the parity-class paths above)
+    return conv3x3_fwd_dispatch(workspace, Cout, w_dgrad, nullptr, dx, lddx, N, H, W, /*Cin=*/Cout, /*Cout=*/Cin, 1, WU_ACT_NONE,
+                                nullptr, 0, 0, egate, ldegate, egate_act, 1, dtype, stream);
 }

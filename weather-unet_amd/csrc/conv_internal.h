@@ -37,3 +37,10 @@ int conv_small_launch(const void* x, int ldx, const void* w_packed, const float*
                       // w_chunked: weights in chunk-major order (wu_conv3x3_small_fwd); mode 0 = launch where the dispatch rule prefers this kernel,
                       // 1 = only answer whether it would, 2 = launch whatever the rule says
                       int w_chunked = 0, int mode = 0);
+
+// internal: wu_conv3x3_fwd with the switch of the stride-2 data gradient (conv3x3_mfma.hip): late_gate = 1 applies a bf16 LeakyReLU gate in
+// front of the one rounding (register-staged template only)
+int conv3x3_fwd_dispatch(const void* x, int ldx, const void* w_packed, const float* bias, void* y, int ldy,
+                         int N, int H, int W, int Cin, int Cout, int stride, int act,
+                         const void* mask, int ldmask, int mask_act,
+                         const void* egate, int ldegate, int egate_act, int late_gate, int dtype, void* stream);
