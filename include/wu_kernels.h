@@ -779,6 +779,35 @@ int wu_knn_radii(const float* x, int ldx, int n, int D, int k, int col_splits, v
 int wu_prdc_counts(const float* x, int ldx, int n1, const double* radii_x, const float* y, int ldy, int n2, const double* radii_y, int D,
                    void* workspace, unsigned* A, unsigned* B, unsigned* C, void* stream);
 
+/* ---- Rank-aware Frechet distance on feature rows (wu/frechet.py): Tr sqrt(Sigma1 Sigma2) = ||A B^T||_* / sqrt((n1 - 1)(n2 - 1)) ------------
+ * A, B are the centred rows of x1 (n1 x D fp32, row stride ld1) and x2 (n2 x D, ld2); A B^T is the double-centred cross-Gram matrix of the
+ * raw rows, and its singular values come from a one-sided (Hestenes) Jacobi iteration: no covariance, no matrix square root, any rank.
+ * The "vectors" are the rows of the set with FEWER rows (a tie goes to set 1): ns = min(n1, n2) <= 4096, nl = max(n1, n2) <= 2^21.
+ *   wu_fd_cross_gram     V[i][j] = <p_i, q_j> (64 x 64 tiles on the fp64 matrix cores), then centred in place:
+ *                        V[i][j] = ((V[i][j] - r_i / nl) - c_j / ns) + t / (ns nl), r row sums, c column sums, t their total.  V is the first
+ *                        ns x ld doubles of `workspace`, row-major, ld = wu_fd_ld(n1, n2) >= nl.
+ *   wu_fd_moments        mu (D doubles), dev2[i] = |x_i - mu|^2 (n doubles) and s[0] = sum_i dev2[i]: tr Sigma = s / (n - 1).
+ *   wu_fd_jacobi_sweep   one sweep over the rows of ANY fp64 matrix V (ns x nl, row stride ld): zeroes rotations[0], then N = 2 ceil(ns / 2) - 1
+ *                        launches, one per round-robin step, a workgroup per row pair: step s pairs (N, s) and ((s + k) mod N, (s - k + N)
+ *                        mod N), k = 1 .. (N - 1) / 2; an index >= ns is the phantom of an odd ns.  With alpha = |p|^2, beta = |q|^2,
+ *                        gamma = <p, q> (p the smaller index) and tol = sqrt(nl) 2^-53 a pair is left alone when
+ *                        |gamma| <= tol sqrt(alpha) sqrt(beta); a vector whose squared norm is below 2^-969 (underflow has taken its
+ *                        precision) is stored as zero and left alone; otherwise zeta = (beta - alpha) / (2 gamma),
+ *                        t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) (1 at zeta = 0), c = 1 / sqrt(1 + t^2), s = c t,
+ *                        p <- c p - s q, q <- s p + c q, and rotations[0] grows by one (an integer atomic).  The caller reads rotations[0]
+ *                        after the sweep and stops at 0.  Vectors up to 2048 long stay in registers; longer ones are read twice.
+ *   wu_fd_finish         sigma[i] = sqrt(|v_i|^2) (ns doubles, index order, not sorted) and total[0] = their sum in index order.
+ * Every floating-point sum runs in one fixed order (a thread's elements t, t + 256, .. in order, lanes l += l + off for off = 32 .. 1, the
+ * four waves in wave order; column sums and means row by row): the same inputs give the same bits.  Every launch ends on its own: no grid
+ * barrier, no cooperative launch.  workspace: wu_fd_workspace_bytes(n1, n2, D) bytes (V, then r, c, t); 0, and wu_fd_ld 0, for arguments
+ * out of range.  Stream-ordered, caller-owned buffers, no allocation, no synchronisation.  n1, n2 >= 2, ld >= D >= 1. */
+int wu_fd_ld(int n1, int n2);
+size_t wu_fd_workspace_bytes(int n1, int n2, int D);
+int wu_fd_cross_gram(const float* x1, int ld1, int n1, const float* x2, int ld2, int n2, int D, void* workspace, void* stream);
+int wu_fd_moments(const float* x, int ldx, int n, int D, double* mu, double* dev2, double* s, void* stream);
+int wu_fd_jacobi_sweep(double* V, int ld, int ns, int nl, unsigned* rotations, void* stream);
+int wu_fd_finish(const double* V, int ld, int ns, int nl, double* sigma, double* total, void* stream);
+
 /* ---- Paired content preservation (wu/paired.py): SSIM / MS-SSIM means and error sums of x against R conditioned outputs y --------------
  * x (B, C, H, W) with ELEMENT strides (xs_n, xs_c, xs_h, xs_w), y (R, B, C, H, W) with (ys_r, ys_n, ys_c, ys_h, ys_w); dtype WU_F32, WU_BF16
  * or WU_SSIM_U8.  A value is widened to fp64 and mapped v * scale + shift; L is the data range, C1 = (K1 L)^2, C2 = (K2 L)^2.  `window` is a

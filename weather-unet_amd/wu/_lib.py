@@ -158,6 +158,12 @@ SIGNATURES = {
     "wu_prdc_workspace_bytes": (SZ, [I, I, I, I]),
     "wu_knn_radii": (I, [P, I, I, I, I, I, P, P, P]),
     "wu_prdc_counts": (I, [P, I, I, P, P, I, I, P, I, P, P, P, P, P]),
+    "wu_fd_ld": (I, [I, I]),
+    "wu_fd_workspace_bytes": (SZ, [I, I, I]),
+    "wu_fd_cross_gram": (I, [P, I, I, P, I, I, I, P, P]),
+    "wu_fd_moments": (I, [P, I, I, I, P, P, P, P]),
+    "wu_fd_jacobi_sweep": (I, [P, I, I, I, P, P]),
+    "wu_fd_finish": (I, [P, I, I, I, P, P, P]),
     "wu_ssim_workspace_bytes": (SZ, [I, I, I, I, I, I, I]),
     "wu_ssim_tile_h": (I, []),
     "wu_ssim_tile_w": (I, []),

@@ -15,6 +15,10 @@ on the fp64 matrix cores), the metric to read on a few hundred images, where the
 themselves: a ``.npz`` PATH must then hold ``features`` (``wu.features.FeatureBank.save_npz``); ``mu`` / ``sigma`` are computed from the rows
 when the file lacks them.
 
+``--fid-rows`` adds the rank-aware Frechet distance of the same rows (wu.frechet: Tr sqrt(sigma1 sigma2) as the nuclear norm of the centred
+cross-Gram matrix, by a Jacobi iteration on the GPU), printed as ``FID (rows): <value> (<sweeps> sweeps)`` after the FID line: no 2048 x 2048
+covariance and no sqrtm, so it is exact on a few hundred images.  It needs ``features`` in a ``.npz`` PATH just as ``--kid`` does.
+
 ``--prdc`` adds improved precision / recall and density / coverage (wu.prdc: k-NN manifold membership on the same rows, PATH1 the real
 set), which tell a loss of diversity from a loss of fidelity; it needs ``features`` in a ``.npz`` PATH just as ``--kid`` does.
 """
@@ -276,14 +280,22 @@ def main(argv=None):
     ap.add_argument("--kid-subset-size", type=int, default=1000,
                     help="with --kid: rows per subset; an error, never clamped, when either path has fewer images")
     ap.add_argument("--kid-seed", type=int, default=2020, help="with --kid: seed of the subset draw (numpy RandomState)")
+    ap.add_argument("--fid-rows", action="store_true",
+                    help="also print the rank-aware Frechet distance computed from the feature rows on the GPU (wu.frechet: singular values "
+                         "of the centred cross-Gram matrix, exact where the covariances are rank-deficient) and its Jacobi sweep count; a "
+                         ".npz path must then hold 'features'")
     ap.add_argument("--prdc", action="store_true",
                     help="also print improved precision / recall and density / coverage of the second path against the first (the real "
                          "set); a .npz path must then hold 'features'")
     ap.add_argument("--prdc-k", type=int, default=5, help="with --prdc: the k of the k-NN radii (prdc's default 5; Kynkaanniemi et al. use 3)")
     args = ap.parse_args(argv)
     stats, banks = _pass_over_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png,
-                                    args.gpu_entropy, fid=True, rows=args.kid or args.prdc)
+                                    args.gpu_entropy, fid=True, rows=args.kid or args.prdc or args.fid_rows)
     print(f"FID: {calculate_frechet_distance(*stats[0], *stats[1])}")
+    if args.fid_rows:
+        from .frechet import frechet_distance
+        r = frechet_distance(*banks)
+        print(f"FID (rows): {r.fid} ({r.sweeps} sweeps)")
     if args.kid:
         from .kid import kernel_inception_distance
         kid_mean, kid_std = kernel_inception_distance(*banks, num_subsets=args.kid_subsets, subset_size=args.kid_subset_size, seed=args.kid_seed)
