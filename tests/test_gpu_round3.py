@@ -619,6 +619,17 @@ def test_spectral_norm_multi_is_bitwise_the_single_weight_path(power_iter):
         sigma = torch.dot(u_ref, wm @ v_ref)
         assert torch.allclose(b[0][i], ws[i] / sigma, rtol=2e-5, atol=1e-7)
         assert torch.allclose(b[1][i], u_ref, rtol=1e-4, atol=1e-6) and torch.allclose(b[2][i], v_ref, rtol=1e-4, atol=1e-6)
+    # and against stock torch.nn.utils.spectral_norm in float64 with the derived running error bound of tests/_sn_ref.py, the weight
+    # GRADIENT included (the lines above never saw it).  The empirical tolerances above stay: a worst-case bound over a 512-term dot
+    # product is wider than they are at the large shapes, and nothing this test asserted may weaken.
+    import _sn_ref as R
+    for i in range(len(ws)):
+        W, G = ws[i].cpu().numpy().reshape(rows[i], -1), gs[i].cpu().numpy().reshape(rows[i], -1)
+        u0, v0 = us[i].cpu().numpy(), vs[i].cpu().numpy()
+        ref = R.StockSN(W, 1e-12).step(u0, v0, power_iter, G)
+        fb = R.forward_bounds(W, u0, v0, power_iter)
+        got = dict(w_eff=b[0][i].cpu().numpy(), u=b[1][i].cpu().numpy(), v=b[2][i].cpu().numpy(), dw=b[3][i].cpu().numpy())
+        R.check_tolerance(f"SNDisc weight {i} {shapes[i]}", ref, fb, got, R.backward_bounds(G, W, fb))
 
 
 def test_sndisc_batched_normalisation_matches_per_layer_path():
