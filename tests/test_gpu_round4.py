@@ -584,7 +584,8 @@ def test_unet_forward_with_and_without_the_fused_head():
 ])
 def test_small_image_conv_vs_generic_and_fp32(case):
     """Same products, another summation grouping (the K range split between wave pairs): within two bf16 ulps of the generic template's
-    output and as close to an fp32 conv of the same bf16 operands as that one is."""
+    output and as close to an fp32 conv of the same bf16 operands as that one is.  (On integer operands the same kernel, its three template
+    instances and the generic template are pinned bit for bit, on channel slices, in tests/test_gpu_conv_s1_exact.py.)"""
     import torch.nn.functional as F
     from wu import _lib, kernels as K
     from wu.layout import as_nhwc
