@@ -832,6 +832,42 @@ int wu_ssim_pairs(const void* x, long long xs_n, long long xs_c, long long xs_h,
                   double scale, double shift, double L, double K1, double K2, const double* window, int k, int levels,
                   void* workspace, double* ssim_mean, double* cs_mean, double* err, double* ssim_map, void* stream);
 
+/* ---- Sliced Wasserstein distance on Laplacian-pyramid patches (wu/swd.py; Karras et al. 2018) ------------------------------------------
+ * Four stages, each stream-ordered on caller-owned buffers, no allocation, no synchronisation, no floating-point atomics: the same inputs
+ * give the same bits.  tests/_swd_ref.py restates the arithmetic.  All pyramid arithmetic in fp64, every operation rounded on its own.
+ *   wu_swd_descriptors   x (N, 3, H, W) with ELEMENT strides, dtype WU_F32, WU_BF16 or WU_SSIM_U8; a value is widened and mapped
+ *                        v * scale + shift.  f = (1, 4, 6, 4, 1) / 16; the blur B is separable, along H first and then along W, taps in
+ *                        ascending order, the border mirrored without repeating the edge sample (i < 0 -> -i, i >= n -> 2 (n - 1) - i).
+ *                        G_0 = x, G_{l+1}[y, x] = B(G_l)[2y, 2x]; U_l = the same pass with taps 2 f over G_{l+1} with zeros stuffed between
+ *                        its samples; L_l = G_l - U_l, L_{levels-1} = G_{levels-1}.  `positions` is a DEVICE array (levels, N, P, 2) of
+ *                        centres (cy, cx), 3 <= cy <= H_l - 4, 3 <= cx <= W_l - 4 (the caller checks them; the kernel clamps).  desc is
+ *                        (levels, N P, 147) float32: descriptor (n, p) of level l holds L_l[n][c][cy - 3 + dy][cx - 3 + dx] at
+ *                        c * 49 + dy * 7 + dx.  Only G_1.. are stored (fp64, in the workspace); L_l is formed at the gathered pixels only.
+ *                        H and W divisible by 2^(levels-1), every level at least 7 x 7, 1 <= levels <= 12, N P <= 2^21.
+ *   wu_swd_normalize     stats[0..2] = mu_c, stats[3..5] = sigma_c: mean and population standard deviation of the 49 m values of channel c,
+ *                        accumulated in fp64 in a fixed order; out = float((double(v) - mu_c) / sigma_c), 0 where sigma_c == 0 (out may be
+ *                        desc itself).
+ *   wu_swd_project_sort  sorted[j][:] = ascending sort of { <desc_i, dirs_j> : i < m } for the ndirs rows of dirs (ndirs, 147): products and
+ *                        sums in fp64 on the fp32 operands (64 x 64 tiles on the fp64 matrix cores), then a segmented sort: blocks of
+ *                        wu_swd_sort_block() keys are sorted on-chip, then merged pairwise over global memory.  dir_chunk directions are
+ *                        handled per pass (0: the library chooses), which only sets the size of the temporary: the result does not depend
+ *                        on it, bit for bit.  workspace: wu_swd_workspace_bytes(m, ndirs, dir_chunk).  1 <= m <= 2^21, 1 <= ndirs <= 4096.
+ *   wu_swd_sort_columns  the sort of wu_swd_project_sort on its own: every row of keys (ncols, m), finite doubles, ascending and in place;
+ *                        workspace: wu_swd_workspace_bytes(m, ncols, ncols) bytes.  Same ranges.
+ *   wu_swd_distance      w[j] = mean_i |a[j][i] - b[j][i]| of two (ndirs, m) arrays, a fixed-order tree sum per direction.
+ * The *_workspace_bytes functions return 0 for anything out of range. */
+int wu_swd_sort_block(void);
+size_t wu_swd_pyramid_workspace_bytes(int N, int H, int W, int levels, int P);
+int wu_swd_descriptors(const void* x, long long xs_n, long long xs_c, long long xs_h, long long xs_w, int dtype, int N, int H, int W,
+                       double scale, double shift, int levels, const int* positions, int P, void* workspace, float* desc, void* stream);
+size_t wu_swd_stats_workspace_bytes(int m);
+int wu_swd_normalize(const float* desc, int m, void* workspace, float* out, double* stats, void* stream);
+size_t wu_swd_workspace_bytes(int m, int ndirs, int dir_chunk);
+int wu_swd_project_sort(const float* desc, int m, const float* dirs, int ndirs, int dir_chunk, void* workspace, double* sorted,
+                        void* stream);
+int wu_swd_sort_columns(double* keys, int m, int ncols, void* workspace, void* stream);
+int wu_swd_distance(const double* a, const double* b, int m, int ndirs, double* w, void* stream);
+
 /* layout helpers for the module boundary: NHWC `dtype` <-> NCHW fp32 (feature maps returned by
  * SNDisc.forward, disc.py:38; gradients flowing back into them). */
 int wu_nhwc_to_nchw_f32(const void* x, int ldx, float* y_nchw, int N, int H, int W, int C, int dtype, void* stream);

@@ -168,6 +168,15 @@ SIGNATURES = {
     "wu_ssim_tile_h": (I, []),
     "wu_ssim_tile_w": (I, []),
     "wu_ssim_pairs": (I, [P] + [ctypes.c_longlong] * 4 + [P] + [ctypes.c_longlong] * 5 + [I] * 6 + [c_double] * 5 + [P, I, I, P, P, P, P, P, P]),
+    "wu_swd_sort_block": (I, []),
+    "wu_swd_pyramid_workspace_bytes": (SZ, [I, I, I, I, I]),
+    "wu_swd_descriptors": (I, [P] + [ctypes.c_longlong] * 4 + [I, I, I, I, c_double, c_double, I, P, I, P, P, P]),
+    "wu_swd_stats_workspace_bytes": (SZ, [I]),
+    "wu_swd_normalize": (I, [P, I, P, P, P, P]),
+    "wu_swd_workspace_bytes": (SZ, [I, I, I]),
+    "wu_swd_project_sort": (I, [P, I, P, I, I, P, P, P]),
+    "wu_swd_sort_columns": (I, [P, I, I, P, P]),
+    "wu_swd_distance": (I, [P, P, I, I, P, P]),
     "wu_prof_begin": (I, [ctypes.c_uint, I]),
     "wu_prof_query": (I, [I, POINTER(c_int), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "wu_prof_end": (I, []),

@@ -8,11 +8,14 @@
 * ``EstimatorEval``          eval_estimator.py:141-159         the estimator on the photographs themselves: mean / std of pred - target, MSE
 * ``ContentPreservation``    (no counterpart in the reference) SSIM / MS-SSIM / MSE / PSNR / MAE between every image and its transferred versions,
                                                                per row; the two transfer evaluations feed it through ``content=``
+* ``SlicedWasserstein``      (no counterpart in the reference) the sliced Wasserstein distance on Laplacian-pyramid patches (``wu.swd``) between
+                                                               the photographs and their transferred versions, per pyramid level; fed
+                                                               through ``swd=``
 
 No pandas, plotting or path conventions: callers feed batches (e.g. from ``wu.data.JpegBatchLoader``).  Every ``update`` accumulates on the
 device and never synchronises with the host; ``confusion`` / ``report`` / ``result`` read the accumulators back.  The generator and the
 networks run in whatever train / eval mode they are in (the reference's scripts leave the generator's Dropout active and call ``.eval()`` on
-the classifier / estimator).  Not a hot path: torch arithmetic on a few numbers per image; the one kernel behind it is ``wu.paired``'s.
+the classifier / estimator).  Not a hot path: torch arithmetic on a few numbers per image; the kernels behind it are ``wu.paired``'s and ``wu.swd``'s.
 """
 import torch
 
@@ -132,6 +135,56 @@ class ContentPreservation:
                 "psnr": 10.0 * torch.log10(self.data_range * self.data_range / m[:, 2]), "count": self.count}
 
 
+class SlicedWasserstein:
+    """At which spatial scale do the outputs depart from the photographs?  ``wu.swd`` accumulated over a data set.  ``update(real, fake)``:
+    real (B, 3, H, W), fake (B, 3, H, W) or (R, B, 3, H, W) as ``sweep`` returns it (R and the image size fixed across calls); the raw
+    descriptors of the batch are gathered and kept on the device, 75 KB per image and level, no host synchronisation.  Image i of the
+    stream gets the positions ``wu.swd.draw`` gives image i, so any split into batches equals one call on the concatenation, bit for bit.
+    ``compute()`` normalises, projects, sorts and reports: a ``wu.swd.SWDResult`` (per-level values x 1e3, finest level first, and their
+    mean), or a list of R of them when ``fake`` came with rows."""
+
+    def __init__(self, P=128, repeats=4, dirs_per_repeat=128, seed=0, value_range=(-1, 1), levels=None, dir_chunk=0):
+        self.P, self.ndirs, self.seed = int(P), int(repeats) * int(dirs_per_repeat), seed
+        self.value_range, self.levels, self.dir_chunk = value_range, levels, int(dir_chunk)
+        self.count, self.shape, self.rows = 0, None, None
+        self.real, self.fake = [], []
+
+    @torch.no_grad()
+    def update(self, real, fake):
+        from . import swd
+        if not (torch.is_tensor(real) and torch.is_tensor(fake) and real.is_cuda and fake.is_cuda):
+            raise RuntimeError("wu.evaluate.SlicedWasserstein: CUDA tensors only -- no CPU fallback")
+        if real.dim() != 4 or fake.dim() not in (4, 5) or tuple(fake.shape[-4:]) != tuple(real.shape):
+            raise ValueError(f"SlicedWasserstein.update: real (B, 3, H, W) and fake (B, 3, H, W) or (R, B, 3, H, W), got "
+                             f"{tuple(real.shape)} / {tuple(fake.shape)}")
+        b, _, h, w = real.shape
+        rows = fake.shape[0] if fake.dim() == 5 else None
+        if self.shape is None:
+            self.shape, self.rows = (h, w), rows
+            if self.levels is None:
+                self.levels = swd.default_levels(h, w)
+        elif self.shape != (h, w) or self.rows != rows:
+            raise ValueError(f"SlicedWasserstein.update: {h} x {w} with rows {rows} after {self.shape[0]} x {self.shape[1]} with rows {self.rows}")
+        shapes = swd.check_levels(h, w, self.levels)
+        pos, _ = swd.draw(self.seed, self.levels, shapes, b, self.P, self.ndirs, first=self.count)
+        self.real.append(swd.descriptors(real, pos, self.value_range, self.levels))
+        self.fake.append([swd.descriptors(f, pos, self.value_range, self.levels) for f in (fake if rows is not None else fake[None])])
+        self.count += b
+
+    def compute(self):
+        from . import swd
+        if not self.real:
+            raise RuntimeError("no batch has been added yet")
+        shapes = swd.check_levels(*self.shape, self.levels)
+        _, dirs = swd.draw(self.seed, self.levels, shapes, 1, 1, self.ndirs)
+        real = [torch.cat([part[l] for part in self.real]) for l in range(self.levels)]
+        out = []
+        for r in range(len(self.fake[0])):
+            fake = [torch.cat([part[r][l] for part in self.fake]) for l in range(self.levels)]
+            out.append(swd.report(swd.distances(real, fake, dirs, self.dir_chunk).tolist()))
+        return out if self.rows is not None else out[0]
+
+
 class ClassTransferEval(_Confusion):
     """eval_class_transfer.py:106-136.  ``update(batch)`` transfers every image of the batch to every class (``transfer.sweep`` over the
     identity rows: the encoder runs once per batch), runs ``classifier`` over the nc * B outputs in passes of at most ``max_images`` images
@@ -139,11 +192,12 @@ class ClassTransferEval(_Confusion):
     ``for i in range(bs)`` over ``onehot[i]``, i.e. it assumes batch size == number of classes; this one always covers all classes, like
     ``infer_driver.class_sweep``.  ``confusion()``: int64 (nc, nc), rows = target class, columns = predicted class; ``report()``:
     ``classification_report`` of it.  With the generator's dropout active the masks are those of ``sweep`` (the repeated-batch forward).
-    ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per class."""
+    ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per class.
+    ``swd``: a ``SlicedWasserstein`` that receives them too (``update(batch, fakes)``), one result per class."""
 
-    def __init__(self, transfer, classifier, num_classes, max_images=SWEEP_MAX_IMAGES, names=None, content=None):
+    def __init__(self, transfer, classifier, num_classes, max_images=SWEEP_MAX_IMAGES, names=None, content=None, swd=None):
         super().__init__(num_classes, names)
-        self.transfer, self.classifier, self.max_images, self.content = transfer, classifier, int(max_images), content
+        self.transfer, self.classifier, self.max_images, self.content, self.swd = transfer, classifier, int(max_images), content, swd
 
     @torch.no_grad()
     def update(self, batch):
@@ -153,17 +207,20 @@ class ClassTransferEval(_Confusion):
         self.add(torch.arange(nc, device=batch.device).repeat_interleave(b), logits.argmax(1))
         if self.content is not None:
             self.content.add(batch, fakes)
+        if self.swd is not None:
+            self.swd.update(batch, fakes)
 
 
 class EstimatorTransferEval(_Rows):
     """eval_estimator_transfer.py:48-61,129-130.  ``update(batch, ref_signals)`` transfers every image of the batch to every row of
     ``ref_signals`` (R, nc) (``transfer.sweep``), runs ``estimator`` over the outputs and appends, per row, the batch mean of
     ``pred - row`` (:54-57); ``result()``: fp64 ``mean`` and population ``std`` over all appended rows (:129-130) and their ``count``.
-    ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per reference row."""
+    ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per reference row.
+    ``swd``: a ``SlicedWasserstein`` that receives them too (``update(batch, fakes)``), one result per reference row."""
 
-    def __init__(self, transfer, estimator, max_images=SWEEP_MAX_IMAGES, content=None):
+    def __init__(self, transfer, estimator, max_images=SWEEP_MAX_IMAGES, content=None, swd=None):
         super().__init__()
-        self.transfer, self.estimator, self.max_images, self.content = transfer, estimator, int(max_images), content
+        self.transfer, self.estimator, self.max_images, self.content, self.swd = transfer, estimator, int(max_images), content, swd
 
     @torch.no_grad()
     def update(self, batch, ref_signals):
@@ -174,6 +231,8 @@ class EstimatorTransferEval(_Rows):
         self.add((pred - ref.unsqueeze(1)).mean(1))
         if self.content is not None:
             self.content.add(batch, fakes)
+        if self.swd is not None:
+            self.swd.update(batch, fakes)
 
 
 class ClassifierEval(_Confusion):

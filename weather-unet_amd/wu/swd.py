@@ -1,0 +1,349 @@
+"""Sliced Wasserstein distance (SWD) on Laplacian-pyramid patches (Karras et al. 2018, "Progressive growing of GANs", section 5 and its
+``metrics/sliced_wasserstein.py``): one number per spatial scale that says how far the local texture statistics of two image sets are apart.
+Pixels only: no pretrained network, no feature extractor.
+
+    r = swd(images_a, images_b)                         # (N, 3, H, W) each -> SWDResult(levels=(.., .., ..) x 1e3, mean)
+    d = descriptors(images, positions)                  # per level, (N * P, 147) float32 CUDA
+    dn, mu, sigma = normalize(d[0])
+    w = sliced_wasserstein(dn_a, dn_b, dirs)            # (ndirs,) float64 CUDA
+    python -m wu.swd DIR_A DIR_B [--size S] [--patches 128] [--repeats 4] [--dirs 128] [--seed 0] [--gpu-decode]
+
+Semantics, in full (tests/_swd_ref.py restates them in numpy).  All pyramid arithmetic in float64, every operation rounded on its own.
+
+Input.  (N, 3, H, W), float32, bfloat16 or uint8, any strides.  A value is widened and mapped ``v * scale + shift`` with
+``wu.paired.range_mapping(value_range)``.
+
+Filter.  ``f = (1, 4, 6, 4, 1) / 16``.  The blur ``B(g)`` is separable, along H first and then along W, taps in ascending order
+(``a = f[0] v[0]; a = a + f[t] v[t]``), the border mirrored without repeating the edge sample: index ``i < 0 -> -i``,
+``i >= n -> 2 (n - 1) - i`` (scipy's ``mode='mirror'``, numpy's ``reflect``).
+
+Pyramid.  ``G_0`` is the mapped input; ``G_{l+1}[y, x] = B(G_l)[2y, 2x]``; ``Z[2y, 2x] = G_{l+1}[y, x]``, 0 elsewhere, of size 2h x 2w;
+``U_l`` is the same separable pass over ``Z`` with taps ``2 f``, same mirror rule and tap order; ``L_l = G_l - U_l`` for l < levels - 1 and
+``L_{levels-1} = G_{levels-1}``.
+
+Levels.  The default is the number of r in ``min(H, W), min(H, W) // 2, ...`` with r >= 16 (``default_levels``: 5 at 256, 4 at 224, 6 at
+512).  ``check_levels`` raises -- nothing is ever cropped or padded -- when H or W is not divisible by ``2^(levels-1)``, when a level is
+smaller than 7 in either dimension, or when ``levels < 1``.
+
+Descriptors.  P per image and level (128 by default).  Descriptor (n, p) of level l is the 3 x 7 x 7 neighbourhood of ``L_l[n]`` centred at
+``positions[l, n, p] = (cy, cx)`` with ``3 <= cy <= H_l - 4`` and ``3 <= cx <= W_l - 4``, flattened as ``c * 49 + dy * 7 + dx`` and rounded
+to float32.  Positions come from the host.
+
+Normalisation.  Per level and per set, over all ``m = N P`` descriptors: for channel c, ``mu_c`` and ``sigma_c`` are the mean and the
+population standard deviation of its 49 m float32 values, accumulated in float64; the value becomes ``float32((double(v) - mu_c) /
+sigma_c)``.  Where ``sigma_c == 0`` the channel's values become 0 -- a departure from PGGAN, which divides by zero there.
+
+Draws (``draw``).  ``rng = np.random.RandomState(seed)``.  First the directions: ``rng.randn(147, ndirs)``, columns normalised to unit
+length in float64, ``.astype(float32)``; they are returned transposed, (ndirs, 147), one direction per row.  Then the positions, image by
+image: for image i = 0, 1, .. and, inside it, level l = 0 .. levels - 1, ``cy = rng.randint(3, H_l - 3, size=P)`` and then
+``cx = rng.randint(3, W_l - 3, size=P)``.  Image i's positions therefore do not depend on how many images follow it; ``first=k`` returns the
+positions of images k .. k + n - 1 of that one sequence, which is how ``wu.evaluate.SlicedWasserstein`` makes two batches equal one call.
+Both sets of a comparison use the same positions and directions.
+
+Distance.  For direction j: ``a = sort(D1 @ dir_j)``, ``b = sort(D2 @ dir_j)``, products and sums in float64 on the float32 operands;
+``w_j = mean_i |a_i - b_i|``; the level's SWD is ``mean_j w_j``.  ``swd`` reports it times 1e3, as PGGAN's tables do, and the mean over
+levels.  ``m1 != m2`` raises.  Inputs must be finite.
+
+Kernels (csrc/swd.hip): the pyramid keeps only G_1.. in float64 (a third of the input), forms L_l at the gathered pixels only, projects in
+64 x 64 tiles on the fp64 matrix cores, sorts every (direction, set) column with an on-chip bitonic block sort and global merge passes, and
+sums in fixed orders: no atomics, two runs give the same bits, and ``dir_chunk`` (how many directions are in flight) changes the memory
+in use and nothing else.  CUDA tensors only: there is no CPU fallback."""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib
+from .layout import stream_ptr
+from .paired import U8, range_mapping
+
+D = 147
+PATCH = 7
+MIN_SIZE = 16                           # the smallest resolution that still gets a default level
+MAX_M, MAX_DIRS = 1 << 21, 4096
+PAIR_BYTES = 1 << 30                    # sliced_wasserstein keeps at most this many bytes of sorted columns (both sets) alive at once
+_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.uint8: U8}
+
+SWDResult = collections.namedtuple("SWDResult", "levels mean")
+
+
+def default_levels(h, w):
+    """The number of r in min(h, w), min(h, w) // 2, ... with r >= 16."""
+    r, n = min(int(h), int(w)), 0
+    while r >= MIN_SIZE:
+        n += 1
+        r //= 2
+    return n
+
+
+def check_levels(h, w, levels):
+    """ValueError unless a pyramid of ``levels`` levels exists for h x w without cropping or padding; returns [(H_l, W_l)]."""
+    h, w, levels = int(h), int(w), int(levels)
+    if levels < 1:
+        raise ValueError(f"swd: levels {levels} must be at least 1 (an image of {h} x {w} has {default_levels(h, w)} by default)")
+    step = 1 << (levels - 1)
+    if h % step or w % step:
+        raise ValueError(f"swd: {h} x {w} is not divisible by 2^(levels-1) = {step}; resize first, nothing is cropped or padded")
+    if h // step < PATCH or w // step < PATCH:
+        raise ValueError(f"swd: level {levels - 1} of {h} x {w} is {h // step} x {w // step}, smaller than the {PATCH} x {PATCH} patch")
+    return [(h >> l, w >> l) for l in range(levels)]
+
+
+def draw(seed, levels, shapes, n, P, ndirs, first=0):
+    """(positions, dirs): int32 (levels, n, P, 2) centres (cy, cx) and float32 (ndirs, 147) unit directions, in the order the module
+    docstring fixes.  shapes: [(H_l, W_l)] per level."""
+    if len(shapes) != levels or n < 1 or P < 1 or ndirs < 1 or first < 0:
+        raise ValueError(f"draw: {len(shapes)} shapes for {levels} levels, n {n}, P {P}, ndirs {ndirs}, first {first}")
+    rng = np.random.RandomState(seed)
+    d = rng.randn(D, ndirs)
+    d = d / np.sqrt(np.sum(np.square(d), axis=0, keepdims=True))
+    dirs = np.ascontiguousarray(d.astype(np.float32).T)
+    pos = np.empty((levels, n, P, 2), dtype=np.int32)
+    for i in range(first + n):
+        for l, (hl, wl) in enumerate(shapes):
+            cy = rng.randint(3, hl - 3, size=P)
+            cx = rng.randint(3, wl - 3, size=P)
+            if i >= first:
+                pos[l, i - first, :, 0] = cy
+                pos[l, i - first, :, 1] = cx
+    return pos, dirs
+
+
+def _require_cuda(*tensors):
+    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        raise RuntimeError("wu.swd: CUDA tensors only -- no CPU fallback")
+
+
+def descriptors(images, positions, value_range=(-1, 1), levels=None):
+    """The raw descriptors of every level: a list of (N * P, 147) float32 CUDA tensors (views of one buffer).  images (N, 3, H, W) float32,
+    bfloat16 or uint8, any strides; positions (levels, N, P, 2) as ``draw`` returns them (numpy or tensor)."""
+    _require_cuda(images)
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"descriptors: images must be (N, 3, H, W), got {tuple(images.shape)}")
+    if images.dtype not in _DTYPES:
+        raise ValueError(f"descriptors: float32, bfloat16 or uint8, got {images.dtype}")
+    n, _, h, w = images.shape
+    if levels is None:
+        levels = default_levels(h, w)
+    shapes = check_levels(h, w, levels)
+    pos = positions.cpu().numpy() if torch.is_tensor(positions) else np.asarray(positions)
+    if pos.ndim != 4 or pos.shape[0] != levels or pos.shape[1] != n or pos.shape[3] != 2 or pos.shape[2] < 1:
+        raise ValueError(f"descriptors: positions must be (levels {levels}, N {n}, P, 2), got {pos.shape}")
+    P = pos.shape[2]
+    for l, (hl, wl) in enumerate(shapes):
+        cy, cx = pos[l, :, :, 0], pos[l, :, :, 1]
+        if cy.min() < 3 or cy.max() > hl - 4 or cx.min() < 3 or cx.max() > wl - 4:
+            raise ValueError(f"descriptors: a position of level {l} ({hl} x {wl}) leaves 3 <= cy <= {hl - 4}, 3 <= cx <= {wl - 4}")
+    scale, shift, _ = range_mapping(value_range)
+    images = images.detach()
+    lib = _lib.load()
+    dev = images.device
+    nbytes = lib.wu_swd_pyramid_workspace_bytes(n, h, w, levels, P)
+    if nbytes == 0:
+        raise ValueError(f"descriptors: N {n} P {P} H {h} W {w} levels {levels} out of the kernel's range (N P <= {MAX_M})")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    pos_d = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.int32)).to(dev)
+    out = torch.empty(levels, n * P, D, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("wu_swd_descriptors", images.data_ptr(), *images.stride(), _DTYPES[images.dtype], n, h, w, scale, shift, levels,
+                  pos_d.data_ptr(), P, ws.data_ptr(), out.data_ptr(), stream_ptr())
+    return [out[l] for l in range(levels)]
+
+
+def _rows(desc, what):
+    _require_cuda(desc)
+    if desc.dim() != 2 or desc.shape[1] != D or desc.dtype != torch.float32:
+        raise ValueError(f"{what}: (m, 147) float32 descriptors, got {tuple(desc.shape)} {desc.dtype}")
+    return desc.detach().contiguous()
+
+
+def normalize(desc):
+    """(desc_n, mu, sigma): the descriptors of one level and one set normalised per channel, and the three means and three population
+    standard deviations as float64 CUDA tensors."""
+    desc = _rows(desc, "normalize")
+    m = desc.shape[0]
+    lib = _lib.load()
+    nbytes = lib.wu_swd_stats_workspace_bytes(m)
+    if nbytes == 0:
+        raise ValueError(f"normalize: m {m} out of the kernel's range 1..{MAX_M}")
+    dev = desc.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty_like(desc)
+    stats = torch.empty(6, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("wu_swd_normalize", desc.data_ptr(), m, ws.data_ptr(), out.data_ptr(), stats.data_ptr(), stream_ptr())
+    return out, stats[:3], stats[3:]
+
+
+def sorted_projections(desc, dirs, dir_chunk=0):
+    """(ndirs, m) float64 CUDA: row j is the ascending sort of ``desc @ dirs[j]``."""
+    desc, dirs = _rows(desc, "sorted_projections"), _rows(dirs, "sorted_projections")
+    m, nd = desc.shape[0], dirs.shape[0]
+    lib = _lib.load()
+    nbytes = lib.wu_swd_workspace_bytes(m, nd, int(dir_chunk))
+    if nbytes == 0:
+        raise ValueError(f"sorted_projections: m {m} (1..{MAX_M}), ndirs {nd} (1..{MAX_DIRS}) or dir_chunk {dir_chunk} out of range")
+    dev = desc.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(nd, m, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("wu_swd_project_sort", desc.data_ptr(), m, dirs.data_ptr(), nd, int(dir_chunk), ws.data_ptr(), out.data_ptr(), stream_ptr())
+    return out
+
+
+def sort_columns(keys):
+    """The segmented sort on its own: every row of the contiguous (ncols, m) float64 CUDA tensor ``keys`` ascending, IN PLACE; returns it."""
+    _require_cuda(keys)
+    if keys.dim() != 2 or keys.dtype != torch.float64 or not keys.is_contiguous():
+        raise ValueError(f"sort_columns: a contiguous (ncols, m) float64 tensor, got {tuple(keys.shape)} {keys.dtype}")
+    nc, m = keys.shape
+    nbytes = _lib.load().wu_swd_workspace_bytes(m, nc, nc)
+    if nbytes == 0:
+        raise ValueError(f"sort_columns: m {m} (1..{MAX_M}) or ncols {nc} (1..{MAX_DIRS}) out of range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+    with torch.cuda.device(keys.device):
+        _lib.call("wu_swd_sort_columns", keys.data_ptr(), m, nc, ws.data_ptr(), stream_ptr())
+    return keys
+
+
+def sliced_wasserstein(d1, d2, dirs, dir_chunk=0):
+    """(ndirs,) float64 CUDA: ``w_j = mean_i |sort(d1 @ dir_j)_i - sort(d2 @ dir_j)_i|``.  d1, d2 (m, 147) float32 normalised descriptors,
+    dirs (ndirs, 147) float32 (numpy or CUDA).  Directions go through in groups, so the sorted columns of both sets never take more than
+    about ``PAIR_BYTES``; inside a group the library handles ``dir_chunk`` directions per pass (0: its own choice).  Neither changes a bit
+    of the result."""
+    if not torch.is_tensor(dirs):
+        _require_cuda(d1, d2)
+        dirs = torch.from_numpy(np.ascontiguousarray(dirs, dtype=np.float32)).to(d1.device)
+    d1, d2, dirs = _rows(d1, "sliced_wasserstein"), _rows(d2, "sliced_wasserstein"), _rows(dirs, "sliced_wasserstein")
+    if d1.shape[0] != d2.shape[0]:
+        raise ValueError(f"sliced_wasserstein: {d1.shape[0]} descriptors against {d2.shape[0]}; unequal counts are not supported")
+    m, nd = d1.shape[0], dirs.shape[0]
+    if not (1 <= m <= MAX_M and 1 <= nd <= MAX_DIRS) or dir_chunk < 0:
+        raise ValueError(f"sliced_wasserstein: m {m} (1..{MAX_M}), ndirs {nd} (1..{MAX_DIRS}) or dir_chunk {dir_chunk} out of range")
+    group = max(1, min(nd, PAIR_BYTES // (16 * m)))
+    w = torch.empty(nd, dtype=torch.float64, device=d1.device)
+    with torch.cuda.device(d1.device):
+        for j0 in range(0, nd, group):
+            a = sorted_projections(d1, dirs[j0:j0 + group], dir_chunk)
+            b = sorted_projections(d2, dirs[j0:j0 + group], dir_chunk)
+            _lib.call("wu_swd_distance", a.data_ptr(), b.data_ptr(), m, a.shape[0], w[j0:].data_ptr(), stream_ptr())
+    return w
+
+
+def report(level_values):
+    """SWDResult of the per-level distances (any iterable of numbers): each times 1e3, and their mean."""
+    lv = tuple(float(v) * 1e3 for v in level_values)
+    return SWDResult(lv, float(np.mean(lv)))
+
+
+def distances(desc_a, desc_b, dirs, dir_chunk=0):
+    """Per level: normalise both sets' raw descriptors, project, sort, and take the mean over directions -> (levels,) float64 CUDA."""
+    out = []
+    for da, db in zip(desc_a, desc_b):
+        out.append(sliced_wasserstein(normalize(da)[0], normalize(db)[0], dirs, dir_chunk).mean())
+    return torch.stack(out)
+
+
+def swd(images_a, images_b, P=128, repeats=4, dirs_per_repeat=128, seed=0, value_range=(-1, 1), levels=None, dir_chunk=0):
+    """SWDResult(levels, mean): the sliced Wasserstein distance x 1e3 of two image sets of one size and count, per pyramid level (finest
+    first) and averaged.  Both sets use the same positions and the same ``repeats * dirs_per_repeat`` directions, drawn from ``seed``."""
+    _require_cuda(images_a, images_b)
+    if images_a.dim() != 4 or tuple(images_a.shape) != tuple(images_b.shape):
+        raise ValueError(f"swd: two sets of one shape (N, 3, H, W), got {tuple(images_a.shape)} / {tuple(images_b.shape)}; unequal counts "
+                         "are not supported")
+    n, _, h, w = images_a.shape
+    if levels is None:
+        levels = default_levels(h, w)
+    shapes = check_levels(h, w, levels)
+    pos, dirs = draw(seed, levels, shapes, n, int(P), int(repeats) * int(dirs_per_repeat))
+    da = descriptors(images_a, pos, value_range, levels)
+    db = descriptors(images_b, pos, value_range, levels)
+    return report(distances(da, db, dirs, dir_chunk).tolist())
+
+
+# ----------------------------------------------------------------------------------------------
+# command line
+# ----------------------------------------------------------------------------------------------
+def _read_dir(files, size, gpu_decode, device, batch_size=64):
+    """The files as uint8 NHWC batches (read through their strides), or as (N, 3, S, S) float32 in [-1, 1] with ``size``."""
+    from PIL import Image
+    dec = pipe = None
+    if gpu_decode:
+        from .jpeg import GPUJpegDecoder
+        dec = GPUJpegDecoder()
+    if size:
+        from .input_pipeline import GPUInputPipeline
+        pipe = GPUInputPipeline(size, train=False)
+    try:
+        for i in range(0, len(files), batch_size):
+            part = files[i:i + batch_size]
+            if dec is not None:
+                batch, sizes = dec.decode_batch(part)
+            else:
+                arrays = [np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8) for f in part]
+                sizes = [a.shape[:2] for a in arrays]
+                hm, wm = max(s[0] for s in sizes), max(s[1] for s in sizes)
+                host = np.zeros((len(arrays), hm, wm, 3), dtype=np.uint8)
+                for k, a in enumerate(arrays):
+                    host[k, :a.shape[0], :a.shape[1]] = a
+                batch = torch.from_numpy(host).to(device)
+            if pipe is not None:
+                yield pipe(batch.contiguous(), [tuple(int(v) for v in s) for s in sizes]), (-1, 1)
+            else:
+                if any(tuple(s) != tuple(sizes[0]) for s in sizes):
+                    raise ValueError(f"images of different sizes ({sorted(set(tuple(int(v) for v in s) for s in sizes))}): give --size")
+                yield batch.permute(0, 3, 1, 2), "uint8"
+    finally:
+        if dec is not None:
+            dec.close()
+
+
+def swd_of_dirs(dir_a, dir_b, size=None, P=128, repeats=4, dirs_per_repeat=128, seed=0, gpu_decode=False, device="cuda:0", log=print):
+    """SWDResult of the .jpg / .png files of two directories, and the number of images used per set.  Images are resized (through
+    ``wu.input_pipeline``) only with ``size``; otherwise mixed sizes are an error.  Directories of unequal count: a random subset of the
+    larger one, drawn from ``seed``, and a line through ``log`` that says so."""
+    from .evaluate import SlicedWasserstein
+    from .fid import image_files
+    fa, fb = image_files(dir_a), image_files(dir_b)
+    if not fa or not fb:
+        raise RuntimeError(f"no .jpg / .png images in {dir_a if not fa else dir_b}")
+    n = min(len(fa), len(fb))
+    if len(fa) != len(fb):
+        big = fa if len(fa) > n else fb
+        keep = sorted(np.random.RandomState(seed).permutation(len(big))[:n].tolist())
+        log(f"{dir_a} holds {len(fa)} images and {dir_b} {len(fb)}: using a random subset (seed {seed}) of {n} of the larger set, "
+            f"{n} images per set")
+        if big is fa:
+            fa = [fa[i] for i in keep]
+        else:
+            fb = [fb[i] for i in keep]
+    acc = SlicedWasserstein(P=P, repeats=repeats, dirs_per_repeat=dirs_per_repeat, seed=seed)
+    for (xa, ra), (xb, rb) in zip(_read_dir(fa, size, gpu_decode, device), _read_dir(fb, size, gpu_decode, device)):
+        acc.value_range = ra
+        acc.update(xa, xb)
+    return acc.compute(), n
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m wu.swd", description="sliced Wasserstein distance on Laplacian-pyramid patches of two "
+                                 "directories of images (x 1e3, per pyramid level and averaged)")
+    ap.add_argument("dir_a")
+    ap.add_argument("dir_b")
+    ap.add_argument("--size", type=int, default=None, help="resize every image to SIZE x SIZE first (otherwise all must have one size)")
+    ap.add_argument("--patches", type=int, default=128, help="descriptors per image and level")
+    ap.add_argument("--repeats", type=int, default=4)
+    ap.add_argument("--dirs", type=int, default=128, help="directions per repeat")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--gpu-decode", action="store_true", help="read the JPEG files through wu.jpeg.GPUJpegDecoder")
+    args = ap.parse_args(argv)
+    r, n = swd_of_dirs(args.dir_a, args.dir_b, args.size, args.patches, args.repeats, args.dirs, args.seed, args.gpu_decode)
+    for l, v in enumerate(r.levels):
+        print(f"SWD x 1e3, level {l}: {v:.4f}")
+    print(f"SWD x 1e3, mean: {r.mean:.4f}")
+    print(f"images per set: {n}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
