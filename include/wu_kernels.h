@@ -896,6 +896,35 @@ int wu_gif_enc_encode(const uint8_t* frames, long long stride_t, long long strid
                       size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int T, int H, int W, int delay_cs,
                       void* stream);
 
+/* ---- LPIPS perceptual distance (wu/lpips.py; Zhang et al. 2018, net = alex, version 0.1) -------------------------------------------------
+ * tests/_lpips_ref.py restates the arithmetic.  The AlexNet trunk itself runs on wu_conv_kxk_fwd / wu_pool3x3_fwd; these are the two ends.
+ *   wu_lpips_input   src (N, 3, H, W) with ELEMENT strides, src_dtype WU_F32, WU_BF16 or WU_LPIPS_U8 -> dst, the dense (N, H, W, 16) network
+ *                    input in `dtype` storage.  In float32, every operation rounded on its own (no FMA): t = v * scale + offset, then
+ *                    u_c = (t - shift_c) / scale_c with shift = (-.030, -.088, -.188), scale = (.458, .448, .450); channels 3..15 are zero.
+ *   wu_lpips_head    one layer's distance of fx (B, h, w, C) ld = ldx against the R rows of fy (R, B, h, w, C) ld = ldy, row r at
+ *                    fy + r * fy_row_stride elements; `weight` (C,) fp32.  Features are widened to fp64; per pixel, a = fx, b = fy:
+ *                        n_a = sqrt(sum_c a_c^2),  ah_c = a_c / (n_a + 1e-10)  (likewise bh),   d = sum_c w_c (ah_c - bh_c)^2
+ *                    out[r * ldo + b] = (sum over the h w pixels of d) / (h w).  C % 16 == 0, 16 <= C <= 512; ldx, ldy multiples of 8, fx / fy
+ *                    16-byte aligned (a channel slice of a wider buffer is ptr + c0, ld = total channels).
+ *   wu_lpips_pairs   the same distance between all rows of f (R, B, h, w, C): out[(i * R + j) * ldo + b] for i < j, entry (j, i) a copy of it,
+ *                    exact zeros on the diagonal.  A block of 4 / 2 / 1 rows i (for C <= 128 / <= 256 / above) is held in registers while
+ *                    the rows j behind it walk past, each normalised once per block: pair (i, j) is formed exactly as wu_lpips_head forms
+ *                    (x = row i, y = row j), from the direct differences (no Gram identity), so the result of a pair does not depend on
+ *                    R or on how the rows are blocked.  2 <= R <= 64.
+ * A workgroup owns wu_lpips_tile_pixels() pixels of one image: 16 lanes share a pixel, each lane keeps its channels of the normalised x
+ * vector in registers while the rows walk past.  Per-wave partial sums go to `workspace` (wu_lpips_workspace_bytes(B, R, h, w, pairs), 0
+ * for anything out of range) and one wave per output folds them in a fixed order: no atomics, the same inputs give the same bits, and an
+ * entry does not depend on B or R.  Stream-ordered, caller-owned buffers, no allocation, no synchronisation. */
+#define WU_LPIPS_U8 2
+int wu_lpips_tile_pixels(void);
+size_t wu_lpips_workspace_bytes(int B, int R, int h, int w, int pairs);
+int wu_lpips_input(const void* src, long long s_n, long long s_c, long long s_h, long long s_w, int src_dtype, int N, int H, int W,
+                   float scale, float offset, void* dst, int dtype, void* stream);
+int wu_lpips_head(const void* fx, int ldx, const void* fy, int ldy, long long fy_row_stride, const float* weight, int dtype, int B, int R,
+                  int h, int w, int C, void* workspace, double* out, int ldo, void* stream);
+int wu_lpips_pairs(const void* f, int ld, long long row_stride, const float* weight, int dtype, int B, int R, int h, int w, int C,
+                   void* workspace, double* out, int ldo, void* stream);
+
 /* ---- instrumentation (bench.py roofline leg) -------------------------------------------------
  * While enabled, the launchers of the kernel families in `family_mask` (bit f = family f) bracket each
  * launch with hipEvents on the launch stream (events come from a pool created by wu_prof_begin; nothing

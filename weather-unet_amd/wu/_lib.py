@@ -177,6 +177,11 @@ SIGNATURES = {
     "wu_swd_project_sort": (I, [P, I, P, I, I, P, P, P]),
     "wu_swd_sort_columns": (I, [P, I, I, P, P]),
     "wu_swd_distance": (I, [P, P, I, I, P, P]),
+    "wu_lpips_tile_pixels": (I, []),
+    "wu_lpips_workspace_bytes": (SZ, [I, I, I, I, I]),
+    "wu_lpips_input": (I, [P] + [ctypes.c_longlong] * 4 + [I, I, I, I, c_float, c_float, P, I, P]),
+    "wu_lpips_head": (I, [P, I, P, I, ctypes.c_longlong, P, I, I, I, I, I, I, P, P, I, P]),
+    "wu_lpips_pairs": (I, [P, I, ctypes.c_longlong, P, I, I, I, I, I, I, P, P, I, P]),
     "wu_prof_begin": (I, [ctypes.c_uint, I]),
     "wu_prof_query": (I, [I, POINTER(c_int), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "wu_prof_end": (I, []),

@@ -11,11 +11,13 @@
 * ``SlicedWasserstein``      (no counterpart in the reference) the sliced Wasserstein distance on Laplacian-pyramid patches (``wu.swd``) between
                                                                the photographs and their transferred versions, per pyramid level; fed
                                                                through ``swd=``
+* ``PerceptualDistance``     (no counterpart in the reference) LPIPS (``wu.lpips``) between every image and its transferred versions, per row,
+                                                               and the pairwise-diversity score among the rows; fed through ``lpips=``
 
 No pandas, plotting or path conventions: callers feed batches (e.g. from ``wu.data.JpegBatchLoader``).  Every ``update`` accumulates on the
 device and never synchronises with the host; ``confusion`` / ``report`` / ``result`` read the accumulators back.  The generator and the
 networks run in whatever train / eval mode they are in (the reference's scripts leave the generator's Dropout active and call ``.eval()`` on
-the classifier / estimator).  Not a hot path: torch arithmetic on a few numbers per image; the kernels behind it are ``wu.paired``'s and ``wu.swd``'s.
+the classifier / estimator).  Not a hot path: torch arithmetic on a few numbers per image; the kernels behind it are ``wu.paired``'s, ``wu.swd``'s and ``wu.lpips``'s.
 """
 import torch
 
@@ -135,6 +137,40 @@ class ContentPreservation:
                 "psnr": 10.0 * torch.log10(self.data_range * self.data_range / m[:, 2]), "count": self.count}
 
 
+class PerceptualDistance:
+    """Is it still the same scene to a viewer, and does the condition do anything?  ``wu.lpips`` accumulated over a data set.
+    ``add(batch, fakes)``: batch (B, 3, H, W), fakes (R, B, 3, H, W) as ``sweep`` returns them (R fixed across calls); sums kept in fp64 on the
+    device, no host synchronisation.  ``result()``: ``lpips`` (R,) fp64 CPU, the per-row mean over all images of lpips(image, its output);
+    ``diversity``, the mean over all images of the mean pairwise LPIPS among an image's R outputs (None with diversity=False or R = 1);
+    and the image ``count``.  ``lpips_model`` is a ``wu.lpips.LPIPS`` with its weights loaded."""
+
+    def __init__(self, lpips_model, value_range=(-1, 1), diversity=True, max_images=None):
+        self.model, self.value_range, self.diversity = lpips_model, value_range, bool(diversity)
+        self.max_images = max_images
+        self.sums, self.div_sum, self.count = None, None, 0
+
+    @torch.no_grad()
+    def add(self, batch, fakes):
+        from . import lpips
+        if fakes.dim() != 5:
+            raise ValueError(f"PerceptualDistance.add: fakes must be (R, B, 3, H, W), got {tuple(fakes.shape)}")
+        mi = lpips.DEFAULT_MAX_IMAGES if self.max_images is None else self.max_images
+        part = self.model.distance(batch, fakes, self.value_range, max_images=mi).sum(1)          # (R,)
+        if self.sums is not None and self.sums.shape != part.shape:
+            raise ValueError(f"PerceptualDistance.add: {part.shape[0]} rows after {self.sums.shape[0]}")
+        self.sums = part if self.sums is None else self.sums + part
+        if self.diversity and fakes.shape[0] >= 2:
+            d = self.model.diversity(fakes, self.value_range, max_images=mi).sum()
+            self.div_sum = d if self.div_sum is None else self.div_sum + d
+        self.count += batch.shape[0]
+
+    def result(self):
+        if self.sums is None:
+            raise RuntimeError("no batch has been added yet")
+        return {"lpips": (self.sums / self.count).cpu(), "diversity": None if self.div_sum is None else (self.div_sum / self.count).item(),
+                "count": self.count}
+
+
 class SlicedWasserstein:
     """At which spatial scale do the outputs depart from the photographs?  ``wu.swd`` accumulated over a data set.  ``update(real, fake)``:
     real (B, 3, H, W), fake (B, 3, H, W) or (R, B, 3, H, W) as ``sweep`` returns it (R and the image size fixed across calls); the raw
@@ -193,11 +229,13 @@ class ClassTransferEval(_Confusion):
     ``infer_driver.class_sweep``.  ``confusion()``: int64 (nc, nc), rows = target class, columns = predicted class; ``report()``:
     ``classification_report`` of it.  With the generator's dropout active the masks are those of ``sweep`` (the repeated-batch forward).
     ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per class.
-    ``swd``: a ``SlicedWasserstein`` that receives them too (``update(batch, fakes)``), one result per class."""
+    ``swd``: a ``SlicedWasserstein`` that receives them too (``update(batch, fakes)``), one result per class.
+    ``lpips``: a ``PerceptualDistance`` that receives them too (``add(batch, fakes)``), one row per class."""
 
-    def __init__(self, transfer, classifier, num_classes, max_images=SWEEP_MAX_IMAGES, names=None, content=None, swd=None):
+    def __init__(self, transfer, classifier, num_classes, max_images=SWEEP_MAX_IMAGES, names=None, content=None, swd=None, lpips=None):
         super().__init__(num_classes, names)
         self.transfer, self.classifier, self.max_images, self.content, self.swd = transfer, classifier, int(max_images), content, swd
+        self.lpips = lpips
 
     @torch.no_grad()
     def update(self, batch):
@@ -209,6 +247,8 @@ class ClassTransferEval(_Confusion):
             self.content.add(batch, fakes)
         if self.swd is not None:
             self.swd.update(batch, fakes)
+        if self.lpips is not None:
+            self.lpips.add(batch, fakes)
 
 
 class EstimatorTransferEval(_Rows):
@@ -216,11 +256,13 @@ class EstimatorTransferEval(_Rows):
     ``ref_signals`` (R, nc) (``transfer.sweep``), runs ``estimator`` over the outputs and appends, per row, the batch mean of
     ``pred - row`` (:54-57); ``result()``: fp64 ``mean`` and population ``std`` over all appended rows (:129-130) and their ``count``.
     ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per reference row.
-    ``swd``: a ``SlicedWasserstein`` that receives them too (``update(batch, fakes)``), one result per reference row."""
+    ``swd``: a ``SlicedWasserstein`` that receives them too (``update(batch, fakes)``), one result per reference row.
+    ``lpips``: a ``PerceptualDistance`` that receives them too (``add(batch, fakes)``), one row per reference row."""
 
-    def __init__(self, transfer, estimator, max_images=SWEEP_MAX_IMAGES, content=None, swd=None):
+    def __init__(self, transfer, estimator, max_images=SWEEP_MAX_IMAGES, content=None, swd=None, lpips=None):
         super().__init__()
         self.transfer, self.estimator, self.max_images, self.content, self.swd = transfer, estimator, int(max_images), content, swd
+        self.lpips = lpips
 
     @torch.no_grad()
     def update(self, batch, ref_signals):
@@ -233,6 +275,8 @@ class EstimatorTransferEval(_Rows):
             self.content.add(batch, fakes)
         if self.swd is not None:
             self.swd.update(batch, fakes)
+        if self.lpips is not None:
+            self.lpips.add(batch, fakes)
 
 
 class ClassifierEval(_Confusion):
