@@ -925,6 +925,40 @@ int wu_lpips_head(const void* fx, int ldx, const void* fy, int ldy, long long fy
 int wu_lpips_pairs(const void* f, int ld, long long row_stride, const float* weight, int dtype, int B, int R, int h, int w, int C,
                    void* workspace, double* out, int ldo, void* stream);
 
+/* ---- Full-resolution output through the fast colour guided filter (wu/guided.py; He, Sun, Tang 2013; He, Sun 2015) ----------------------
+ * tests/_guided_ref.py restates the arithmetic.  All of it in fp64, every operation rounded on its own (no FMA), no atomics: the same
+ * inputs give the same bits and a row's numbers do not depend on R.  Stream-ordered, caller-owned buffers, no allocation, no
+ * synchronisation.
+ *   wu_guided_coeffs   guide I (N, 3, hl, wl) fp32 with ELEMENT strides, mapped v * g_scale + g_shift; targets p (R, N, 3, hl, wl) of
+ *                      t_dtype WU_F32 or WU_BF16 with ELEMENT strides, mapped v * t_scale + t_shift.  box(v) = the mean over the
+ *                      (2r+1)^2 window clipped to the image: the in-range taps of a row summed left to right, those row sums summed top to
+ *                      bottom, ONE division by count_y * count_x.  Per pixel: mI_k = box(I_k); S_jk = box(I_j I_k) - mI_j mI_k, eps added
+ *                      to the diagonal; with S = [[a b c] [b d e] [c e f]] the cofactors c00 = d f - e e, c01 = c e - b f, c02 = b e - c d,
+ *                      c11 = a f - c c, c12 = b c - a e, c22 = a d - b b, det = (a c00 + b c01) + c c02, inv_jk = c_jk / det.  Per row and
+ *                      output channel c: cov_k = box(I_k p_c) - mI_k box(p_c); a_ck = (inv_k0 cov_0 + inv_k1 cov_1) + inv_k2 cov_2;
+ *                      b_c = box(p_c) - ((a_c0 mI_0 + a_c1 mI_1) + a_c2 mI_2).  coeffs (R, N, 12, hl, wl) fp64: box(a_ck) at map 3 c + k,
+ *                      box(b_c) at map 9 + c.  r >= max(hl, wl) is one global regression.  SIX launches whatever N and R, FIVE for r <= 8 (the
+ *                      last two passes are then one tiled launch; the same bits); the guide's moments and inverse are formed once per image.  `workspace`: wu_guided_workspace_bytes(N, R, hl, wl) bytes.
+ *   wu_guided_apply    photos (N, Hmax, Wmax, 3) uint8, image n of size sizes[2 n] x sizes[2 n + 1] (h, w): `sizes_host` is checked on the
+ *                      host, `sizes_dev` is the same array in device memory, read by the kernel.  Output pixel (Y, X) of image n:
+ *                      vy = (Y + 0.5) (hl / h) - 0.5 clamped to [0, hl - 1], y0 = floor(vy), y1 = min(y0 + 1, hl - 1), fy = vy - y0, the
+ *                      same in x; each coefficient top = v00 + (v01 - v00) fx, bot = v10 + (v11 - v10) fx, top + (bot - top) fy;
+ *                      I_k = byte_k / 255.0; q_c = ((A_c0 I_0 + A_c1 I_1) + A_c2 I_2) + b_c.  Exactly one of out_u8 (R, N, Hmax, Wmax, 3),
+ *                      bytes (int)min(max(q 255, 0), 255) (truncation), and out_f32 (R, N, 3, Hmax, Wmax), (float)q; nothing outside an
+ *                      image's (h, w) is written.  ONE launch: a workgroup owns a wu_guided_tile_h() x wu_guided_tile_w() tile of a
+ *                      photograph, reads its pixels once, keeps the low-resolution coefficients it needs in LDS and walks the R rows.
+ * Argument errors (r < 0, eps <= 0, a zero size, (h, w) beyond (Hmax, Wmax), a NULL pointer, an unknown dtype) return a negative code
+ * before anything touches the device. */
+size_t wu_guided_workspace_bytes(int N, int R, int hl, int wl);      /* 0 for anything out of range */
+int wu_guided_tile_h(void);
+int wu_guided_tile_w(void);
+int wu_guided_coeffs(const float* guide, long long gs_n, long long gs_c, long long gs_h, long long gs_w, double g_scale, double g_shift,
+                     const void* targets, long long ts_r, long long ts_n, long long ts_c, long long ts_h, long long ts_w, int t_dtype,
+                     double t_scale, double t_shift, int N, int R, int hl, int wl, int r, double eps, void* workspace, double* coeffs,
+                     void* stream);
+int wu_guided_apply(const double* coeffs, int N, int R, int hl, int wl, const unsigned char* photos, int Hmax, int Wmax,
+                    const int* sizes_host, const int* sizes_dev, unsigned char* out_u8, float* out_f32, void* stream);
+
 /* ---- instrumentation (bench.py roofline leg) -------------------------------------------------
  * While enabled, the launchers of the kernel families in `family_mask` (bit f = family f) bracket each
  * launch with hipEvents on the launch stream (events come from a pool created by wu_prof_begin; nothing

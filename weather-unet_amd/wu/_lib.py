@@ -182,6 +182,12 @@ SIGNATURES = {
     "wu_lpips_input": (I, [P] + [ctypes.c_longlong] * 4 + [I, I, I, I, c_float, c_float, P, I, P]),
     "wu_lpips_head": (I, [P, I, P, I, ctypes.c_longlong, P, I, I, I, I, I, I, P, P, I, P]),
     "wu_lpips_pairs": (I, [P, I, ctypes.c_longlong, P, I, I, I, I, I, I, P, P, I, P]),
+    "wu_guided_workspace_bytes": (SZ, [I, I, I, I]),
+    "wu_guided_tile_h": (I, []),
+    "wu_guided_tile_w": (I, []),
+    "wu_guided_coeffs": (I, [P] + [ctypes.c_longlong] * 4 + [c_double, c_double, P] + [ctypes.c_longlong] * 5 + [I, c_double, c_double]
+                         + [I] * 5 + [c_double, P, P, P]),
+    "wu_guided_apply": (I, [P, I, I, I, I, P, I, I, P, P, P, P, P]),
     "wu_prof_begin": (I, [ctypes.c_uint, I]),
     "wu_prof_query": (I, [I, POINTER(c_int), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "wu_prof_end": (I, []),

@@ -319,3 +319,97 @@ def save_demo(frames_u8, out, encoder=None, png_encoder=None, ext=".jpg", stem="
     for f in _save_u8_async(frames_u8, paths, encoder, png_encoder):
         f.result()
     return paths
+
+
+# ---- full-resolution output (wu.guided) ------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def transfer_fullres(transfer, photos_u8, sizes, rows, input_size, normalize=True, upsampler=None, shared_encoder=True, graphed=None):
+    """The transfer at the PHOTOGRAPH's resolution: ``photos_u8`` (N, Hmax, Wmax, 3) uint8 with per-image ``sizes`` (h, w), as the decoders
+    leave a batch.  (1) ``GPUInputPipeline(input_size, train=False)`` makes the network input (N, 3, S, S); (2) the sweep over ``rows`` --
+    (R, nc): every image under every row, as ``signal_sweep``; (R, N, nc): every image under its own rows (one row per image, as
+    ``transfer_rows``, is (1, N, nc)) --; (3) the low-resolution target is ``normalize_minmax`` of each output, exactly what ``save_images``
+    would have written, or ``(out + 1) / 2`` with ``normalize=False``; (4) ``upsampler`` (a ``wu.guided.GuidedUpsampler``; default: one with
+    its untuned default r and eps) fits the target to the network input and applies the fit to the photograph.  Returns the padded
+    (R, N, Hmax, Wmax, 3) uint8 batch the encoders take with ``sizes``.  ``shared_encoder`` / ``graphed``: see ``signal_sweep`` (rows of
+    three dimensions need the shared encoder)."""
+    from .guided import GuidedUpsampler
+    from .input_pipeline import GPUInputPipeline
+    batch = GPUInputPipeline(input_size, train=False)(photos_u8, sizes)
+    rows = rows.to(device=batch.device, dtype=torch.float32)
+    if rows.dim() == 3:
+        if rows.shape[1] != batch.shape[0]:
+            raise ValueError(f"transfer_fullres: rows (R, N, nc) for N = {batch.shape[0]} images, got {tuple(rows.shape)}")
+        if not shared_encoder:
+            raise ValueError("transfer_fullres: rows per image (R, N, nc) go through the shared-encoder sweep")
+        out = _sweep(transfer, batch, rows, graphed, None)
+    elif rows.dim() == 2:
+        out = signal_sweep(transfer, batch, rows, False, graphed, shared_encoder)
+    else:
+        raise ValueError(f"transfer_fullres: rows (R, nc) or (R, N, nc), got {tuple(rows.shape)}")
+    out = out.float()
+    low = _normalize_all(out, True) if normalize else (out + 1) / 2
+    up = upsampler if upsampler is not None else GuidedUpsampler()
+    return up.upsample(batch, low, photos_u8, sizes)
+
+
+def _decode_files(files, decoder):
+    """(photos_u8, sizes) of one batch of files: all .jpg / .jpeg through a ``GPUJpegDecoder``, anything else through ``wu.png.decode_mixed``
+    (segmented PNGs on the GPU, the rest by Pillow)."""
+    if all(os.fspath(f).lower().endswith((".jpg", ".jpeg")) for f in files):
+        if decoder is not None:
+            return decoder.decode_batch(files)
+        from .jpeg import GPUJpegDecoder
+        dec = GPUJpegDecoder()
+        try:
+            return dec.decode_batch(files)
+        finally:
+            dec.close()
+    from .png import decode_mixed
+    return decode_mixed(files)
+
+
+def _save_padded_async(u8, sizes, paths, encoder, png_encoder):
+    """``_save_u8_async`` for a padded batch: (N, Hmax, Wmax, 3) uint8 with per-image (h, w)."""
+    ext = os.path.splitext(paths[0])[1].lower()
+    if ext in (".jpg", ".jpeg"):
+        return [(encoder if encoder is not None else _encoder(u8)).save_batch_async(u8, paths, sizes)]
+    if ext == ".png" and png_encoder is not None:
+        return [png_encoder.save_batch_async(u8, paths, sizes)]
+    rgb = u8.cpu().numpy()
+    for i, (h, w) in enumerate(sizes):
+        _pillow_save((rgb[i, :h, :w], paths[i]))
+    return []
+
+
+@torch.no_grad()
+def fullres_sweep_to_dir(transfer, files, src_labels, class_names, out_dir, input_size=224, ext=".jpg", decoder=None, encoder=None,
+                         png_encoder=None, rows=None, row_names=None, normalize=True, upsampler=None, shared_encoder=True, graphed=None):
+    """``class_sweep_to_dir`` at the photographs' own sizes, from files to files: ``files`` are decoded on the GPU (``decoder``: a
+    ``GPUJpegDecoder`` for an all-JPEG list; other lists go through ``wu.png.decode_mixed``), transferred by ``transfer_fullres`` under every
+    class (or under ``rows`` (R, nc) named ``row_names``, default ``row0000``, ...), and written with ``class_sweep_to_dir``'s names,
+    ``{class_names[src_labels[j]]}_{stem of files[j]}_{target name}{ext}`` (without the first part when ``src_labels`` is None), each file
+    h x w like its source: .jpg / .jpeg by ``encoder`` (default: the shared ``GPUJpegEncoder``), .png by ``png_encoder`` when one is passed,
+    any other format by Pillow.  All files exist when this returns; returns the paths, target by target."""
+    files = [os.fspath(f) for f in files]
+    if src_labels is not None and len(src_labels) != len(files):
+        raise ValueError("fullres_sweep_to_dir: one source label per file")
+    photos, sizes = _decode_files(files, decoder)
+    if rows is None:
+        rows = torch.eye(len(class_names), device=photos.device)
+        names = list(class_names)
+    else:
+        names = list(row_names) if row_names is not None else [f"row{r:04d}" for r in range(rows.shape[0])]
+        if len(names) != rows.shape[0]:
+            raise ValueError("fullres_sweep_to_dir: one name per row")
+    out = transfer_fullres(transfer, photos, sizes, rows, input_size, normalize, upsampler, shared_encoder, graphed)
+    os.makedirs(out_dir, exist_ok=True)
+    stems = [os.path.splitext(os.path.basename(f))[0] for f in files]
+    written, pending = [], []
+    for i, name in enumerate(names):
+        paths = [os.path.join(out_dir, (f"{class_names[int(src_labels[j])]}_" if src_labels is not None else "") + f"{stems[j]}_{name}{ext}")
+                 for j in range(len(files))]
+        pending += _save_padded_async(out[i], sizes, paths, encoder, png_encoder)
+        written += paths
+    for f in pending:
+        f.result()
+    return written
