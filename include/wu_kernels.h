@@ -895,6 +895,33 @@ size_t wu_gif_enc_block_stride(int H, int W);
 int wu_gif_enc_encode(const uint8_t* frames, long long stride_t, long long stride_y, long long stride_x, long long stride_c, void* workspace,
                       size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int T, int H, int W, int delay_cs,
                       void* stream);
+/* The same encoder with its quality options; flags == 0 writes the blocks of wu_gif_enc_encode (same stride; the workspace is a little
+ * larger, by the info) through the kernels of the options.  All rules
+ * are integer and restated in tests/_gif_quality_ref.py; still one memset and five launches, stream-ordered, nothing allocated.
+ *   WU_GIF_NEAREST  the index of a pixel is the palette entry, among those in use, at the smallest squared Euclidean distance in 8-bit RGB
+ *                   (lowest index among equals; a brute-force search over the palette in LDS in the LZW kernel's map phase) instead of the
+ *                   median-cut box of its histogram bin.
+ *   WU_GIF_ORDERED  with WU_GIF_NEAREST only: the colour searched is clamp(pixel_c + floor((2 M + 1 - 64) A_c / 128), 0, 255).  M, 0..63, is
+ *                   the 8 x 8 threshold of the pixel's position in the FRAME: with x_b, y_b bit b of x & 7, y & 7,
+ *                   M = sum over b = 0..2 of ((x_b ^ y_b) << 1 | y_b) << 2 (2 - b).  A_c = min(16, 8 (hi_c - lo_c + 1)), lo / hi the final
+ *                   tight 5-bit bounds of the box of the pixel's bin.
+ *   WU_GIF_EXACT    a frame (under WU_GIF_GLOBAL: the animation) with at most 256 distinct colours gets exactly those as its palette, in
+ *                   ascending order of r << 16 | g << 8 | b, zeros behind, index = rank: reproduced bit for bit, no median cut, no dither.
+ *                   The colours are counted in a 1024-slot open-addressed set beside the histogram; 257 colours end the counting.
+ *   WU_GIF_GLOBAL   one histogram, one median cut or exact set and one palette for all T frames (T H W < 2^32): palette_dev receives its 768
+ *                   bytes for a global colour table, and the blocks carry no local table (image descriptor flags 0x00; the fixed part of a
+ *                   block is 8 + 10 + 1 bytes, and wu_gif_enc_block_stride_ex is 768 bytes less).
+ * palette_dev: 768 bytes, needed under WU_GIF_GLOBAL only (else may be null).  info_dev: 2 T ints; info_dev[2 t] = palette entries in use
+ * for frame t, info_dev[2 t + 1] = 1 if the frame took the exact path, else 0. */
+#define WU_GIF_NEAREST 1
+#define WU_GIF_ORDERED 2
+#define WU_GIF_EXACT 4
+#define WU_GIF_GLOBAL 8
+size_t wu_gif_enc_workspace_bytes_ex(int T, int H, int W, int flags);      /* 0: bad shape or flags */
+size_t wu_gif_enc_block_stride_ex(int H, int W, int flags);
+int wu_gif_enc_encode_ex(const uint8_t* frames, long long stride_t, long long stride_y, long long stride_x, long long stride_c, void* workspace,
+                         size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int T, int H, int W, int delay_cs, int flags,
+                         uint8_t* palette_dev, int* info_dev, void* stream);
 
 /* ---- LPIPS perceptual distance (wu/lpips.py; Zhang et al. 2018, net = alex, version 0.1) -------------------------------------------------
  * tests/_lpips_ref.py restates the arithmetic.  The AlexNet trunk itself runs on wu_conv_kxk_fwd / wu_pool3x3_fwd; these are the two ends.

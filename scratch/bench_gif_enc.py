@@ -3,6 +3,12 @@ it -- Pillow's quantiser and LZW on the host over the frames fetched as raw RGB,
 
     python scratch/bench_gif_enc.py [--out FILE.json]
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o gif -- python scratch/bench_gif_enc.py --mode device      # kernel rows, run of its own
+    python scratch/bench_gif_enc.py --mode quality [--paths default,best]        # the quality options against the defaults, same call
+    WU_AB_LIB=scratch/_oldlib/libwu_old.so python scratch/bench_gif_enc.py --mode quality --paths default     # the defaults on another build
+
+--mode quality: ``encode`` (launch + fetch, the file as bytes; nothing written) of the demo table with the default encoder and with
+``GPUGifEncoder.best()``, one warm-up call each, then `--runs` calls each, alternating, device events around the whole call and a
+synchronise behind it; median (min .. max) and the file sizes.  --mode device takes --paths too, for the kernel rows of both.
 
 Shapes: the grid bench's demo table (B=16, nc=5, 256^2, T=8 frames, 14 entries in ping-pong order) and B=4 at 224^2, T=10.  The sources are
 smooth random fields with a little noise on top (bilinear upsampling of 8x8 noise plus 2 % white noise) rather than white noise, which no
@@ -45,7 +51,8 @@ def smooth(shape, g, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", default="all", choices=["all", "device"])
+    ap.add_argument("--mode", default="all", choices=["all", "device", "quality"])
+    ap.add_argument("--paths", default="default", help="--mode quality / device: comma-separated, of default, nearest, ordered, exact, global, best")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -57,6 +64,9 @@ def main():
     g = torch.Generator().manual_seed(0)
     res = {"cmd": " ".join(sys.argv), "gpu": torch.cuda.get_device_name(0), "runs": a.runs}
     enc = GPUGifEncoder(dev)
+    options = {"default": {}, "nearest": dict(mapping="nearest"), "ordered": dict(mapping="nearest", dither="ordered"), "exact": dict(exact=True),
+               "global": dict(palette="global"), "best": dict(mapping="nearest", dither="ordered", exact=True, palette="global")}
+    paths = {k: (enc if k == "default" else GPUGifEncoder(dev, **options[k])) for k in a.paths.split(",")}
     for name, (T, nc, B, S) in {"demo_B16_nc5_256_T8": (8, 5, 16, 256), "demo_B4_nc5_224_T10": (10, 5, 4, 224)}.items():
         batch = smooth((B, 3, S, S), g, dev)
         results = smooth((T, nc, B, 3, S, S), g, dev)
@@ -64,10 +74,30 @@ def main():
         torch.cuda.synchronize()
         row = {"frames": list(frames.shape), "entries": len(ping_pong(T))}
         if a.mode == "device":
-            for _ in range(5):
-                enc.encode(frames, 1000 // T, 0, ping_pong(T))
+            for e in paths.values():
+                for _ in range(5):
+                    e.encode(frames, 1000 // T, 0, ping_pong(T))
             torch.cuda.synchronize()
             res[name] = row
+            continue
+        if a.mode == "quality":
+            ms, size = {k: [] for k in paths}, {}
+            for k, e in paths.items():
+                size[k] = len(e.encode(frames, 1000 // T, 0, ping_pong(T)))
+            for r in range(a.runs):                                          # alternate the paths
+                for k in (list(paths) if r % 2 == 0 else list(paths)[::-1]):
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    paths[k].encode(frames, 1000 // T, 0, ping_pong(T))
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ms[k].append(e0.elapsed_time(e1) * 1e-3)
+            for k in paths:
+                row[k + "_call_ms"] = spread(ms[k])
+                row[k + "_file_bytes"] = size[k]
+            res[name] = row
+            print(name, json.dumps(row), flush=True)
             continue
         with tempfile.TemporaryDirectory() as tmp:
             paths = {"gpu": os.path.join(tmp, "gpu.gif"), "pillow": os.path.join(tmp, "pillow.gif")}

@@ -135,6 +135,10 @@ SIGNATURES = {
     "wu_gif_enc_workspace_bytes": (SZ, [I, I, I]),
     "wu_gif_enc_block_stride": (SZ, [I, I]),
     "wu_gif_enc_encode": (I, [P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, SZ, P, SZ, P, I, I, I, I, P]),
+    "wu_gif_enc_workspace_bytes_ex": (SZ, [I, I, I, I]),
+    "wu_gif_enc_block_stride_ex": (SZ, [I, I, I]),
+    "wu_gif_enc_encode_ex": (I, [P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, SZ, P, SZ, P, I, I, I, I, I, P, P,
+                                 P]),
     "wu_grid_cell_bytes": (SZ, []),
     "wu_grid_workspace_bytes": (SZ, [I, I]),
     "wu_grid_workspace_layout": (I, [I, I, P]),

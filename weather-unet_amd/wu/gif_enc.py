@@ -11,8 +11,17 @@ The files are NOT the bytes Pillow writes (another palette order, one unsegmente
 equal ``tests/_gif_enc_ref.encode`` byte for byte.  The output buffer is sized by the exact worst case (every pixel a 12-bit code), so there
 is no overflow and no Pillow fallback.
 
-Limitation: colours are told apart by their histogram bin, so an image with several distinct colours in one 5-bit bin is not reproduced
-exactly even if it has 256 colours or fewer (a 256-level grey ramp comes out at about 41 dB, where Pillow is exact).
+Limitation of the defaults: colours are told apart by their histogram bin, so an image with several distinct colours in one 5-bit bin is
+not reproduced exactly even if it has 256 colours or fewer (a 256-level grey ramp comes out at about 41 dB, where Pillow is exact), a smooth
+ramp comes out in bands, and every frame has a palette of its own.  The options lift each of these (all integer rules, restated in
+``tests/_gif_quality_ref.py``; they change the file, so they are opt-in):
+
+    mapping="nearest"   index = the nearest palette entry in use (squared distance in 8-bit RGB, lowest index among equals), not the bin's box
+    dither="ordered"    an 8 x 8 ordered dither in front of that search, from the pixel's position only (so it does not flicker between
+                        frames), at most one step of the local palette and at most 16 levels; needs mapping="nearest"
+    exact=True          a frame (or, under a global palette, an animation) of at most 256 colours keeps exactly those colours
+    palette="global"    one palette for all frames in a global colour table: a cell that does not change keeps its colours
+    GPUGifEncoder.best(...)  all four
 
     enc = GPUGifEncoder()
     data = enc.encode(frames, duration_ms=125, loop=0, order=ping_pong(T))      # frames (T, H, W, 3) uint8 on the GPU; bytes
@@ -47,12 +56,32 @@ def block_stride(h, w):
     return n
 
 
+NEAREST, ORDERED, EXACT, GLOBAL = 1, 2, 4, 8     # the flags of wu_gif_enc_encode_ex
+
+
+def option_flags(mapping="box", dither=None, exact=False, palette="local"):
+    """The flags of a set of options; ValueError for anything else.  Host only."""
+    if mapping not in ("box", "nearest"):
+        raise ValueError(f"GPUGifEncoder: mapping must be 'box' or 'nearest', got {mapping!r}")
+    if dither not in (None, "ordered"):
+        raise ValueError(f"GPUGifEncoder: dither must be None or 'ordered', got {dither!r}")
+    if exact is not True and exact is not False:
+        raise ValueError(f"GPUGifEncoder: exact must be True or False, got {exact!r}")
+    if palette not in ("local", "global"):
+        raise ValueError(f"GPUGifEncoder: palette must be 'local' or 'global', got {palette!r}")
+    if dither == "ordered" and mapping != "nearest":
+        raise ValueError("GPUGifEncoder: dither='ordered' requires mapping='nearest'")
+    return (NEAREST if mapping == "nearest" else 0) | (ORDERED if dither else 0) | (EXACT if exact else 0) | (GLOBAL if palette == "global" else 0)
+
+
 class DeviceResult:
     """Result of GPUGifEncoder.launch: the image blocks on the device (frame t at ``out[t * block_stride:]``) and their byte counts in
-    ``result``."""
-    def __init__(self, out, result, workspace, frames, t, h, w, stride):
+    ``result``.  With options also ``info`` (T, 2) int32 -- palette entries in use and whether the frame took the exact path -- and, under
+    a global palette, ``palette``: its 768 bytes."""
+    def __init__(self, out, result, workspace, frames, t, h, w, stride, flags=0, palette=None, info=None):
         self.out, self.result, self.workspace, self.frames = out, result, workspace, frames
         self.t, self.h, self.w, self.block_stride = t, h, w, stride
+        self.flags, self.palette, self.info = flags, palette, info
 
 
 class GPUGifEncoder:
@@ -67,8 +96,14 @@ class GPUGifEncoder:
     Staging buffers: ``wu._codec.StagingPool``.
 
     ``frames``: (T, H, W, 3) uint8 on the GPU, any non-negative strides (what ``wu.grid.demo_tables(..., out="uint8")`` returns).
+
+    ``mapping``, ``dither``, ``exact``, ``palette``: the quality options of the module docstring (``wu_gif_enc_encode_ex``); the defaults
+    write the bytes of ``tests/_gif_enc_ref.encode``, any option those of ``tests/_gif_quality_ref.encode``.  Under ``palette="global"``
+    ``fetch`` also copies the 768 bytes of the palette for the header.  ``best()`` turns all four on.
     """
-    def __init__(self, device="cuda", max_staging=4):
+    def __init__(self, device="cuda", max_staging=4, mapping="box", dither=None, exact=False, palette="local"):
+        self.flags = option_flags(mapping, dither, exact, palette)
+        self.mapping, self.dither, self.exact, self.palette = mapping, dither, exact, palette
         self.device = torch.device(device)
         self.max_staging = int(max_staging)
         self._lock = threading.Lock()
@@ -76,6 +111,11 @@ class GPUGifEncoder:
         self.stats = {"frames": 0, "bytes": 0}
         self._lib = _lib.load()
         self.segment_pixels = int(self._lib.wu_gif_enc_segment_pixels())
+
+    @classmethod
+    def best(cls, device="cuda", max_staging=4):
+        """Every quality option on: nearest-colour mapping, ordered dither, exact small palettes, one global palette."""
+        return cls(device, max_staging, mapping="nearest", dither="ordered", exact=True, palette="global")
 
     def close(self):
         self._staging.clear()
@@ -95,17 +135,30 @@ class GPUGifEncoder:
         st, sy, sx, sc = frames.stride()
         if min(st, sy, sx, sc) < 0:
             raise ValueError("GPUGifEncoder: negative strides")
-        stride = int(self._lib.wu_gif_enc_block_stride(h, w))
-        ws_bytes = int(self._lib.wu_gif_enc_workspace_bytes(t, h, w))
+        flags = self.flags
+        if flags == 0:                                                     # the defaults stay on the first entry points throughout
+            stride, ws_bytes = int(self._lib.wu_gif_enc_block_stride(h, w)), int(self._lib.wu_gif_enc_workspace_bytes(t, h, w))
+        else:
+            stride = int(self._lib.wu_gif_enc_block_stride_ex(h, w, flags))
+            ws_bytes = int(self._lib.wu_gif_enc_workspace_bytes_ex(t, h, w, flags))
         if stride == 0 or ws_bytes == 0:
-            raise ValueError(f"GPUGifEncoder: cannot encode {t} frames of {h} x {w} (at most 65535 on a side and 2^26 pixels)")
+            raise ValueError(f"GPUGifEncoder: cannot encode {t} frames of {h} x {w} (at most 65535 on a side and 2^26 pixels; under a "
+                             "global palette fewer than 2^32 pixels in all)")
+        palette = info = None
         with torch.cuda.device(frames.device):
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=frames.device)
             out = torch.empty(t * stride, dtype=torch.uint8, device=frames.device)
             result = torch.empty(t, dtype=torch.int32, device=frames.device)
-            _lib.call("wu_gif_enc_encode", frames.data_ptr(), st, sy, sx, sc, ws.data_ptr(), ws.numel(), out.data_ptr(), out.numel(),
-                      result.data_ptr(), t, h, w, 0, stream_ptr())
-        return DeviceResult(out, result, ws, frames, t, h, w, stride)
+            if flags == 0:
+                _lib.call("wu_gif_enc_encode", frames.data_ptr(), st, sy, sx, sc, ws.data_ptr(), ws.numel(), out.data_ptr(), out.numel(),
+                          result.data_ptr(), t, h, w, 0, stream_ptr())
+            else:
+                info = torch.empty((t, 2), dtype=torch.int32, device=frames.device)
+                palette = torch.empty(768, dtype=torch.uint8, device=frames.device) if flags & GLOBAL else None
+                _lib.call("wu_gif_enc_encode_ex", frames.data_ptr(), st, sy, sx, sc, ws.data_ptr(), ws.numel(), out.data_ptr(), out.numel(),
+                          result.data_ptr(), t, h, w, 0, flags, palette.data_ptr() if palette is not None else None, info.data_ptr(),
+                          stream_ptr())
+        return DeviceResult(out, result, ws, frames, t, h, w, stride, flags, palette, info)
 
     # ---- host stage ----
     def fetch(self, res, duration_ms, loop=0, order=None):
@@ -126,7 +179,10 @@ class GPUGifEncoder:
             blocks = _codec.fetch_packed(self._staging, res.out, res.block_stride, counts)
         for i, b in enumerate(blocks):
             blocks[i] = b[:4] + struct.pack("<H", delay) + b[6:]         # the graphic control extension's delay
-        head = b"GIF89a" + struct.pack("<HH", res.w, res.h) + b"\x70\x00\x00"
+        if res.flags & GLOBAL:                                             # a 256-entry global colour table; the blocks carry none
+            head = b"GIF89a" + struct.pack("<HH", res.w, res.h) + b"\xF7\x00\x00" + res.palette.cpu().numpy().tobytes()
+        else:
+            head = b"GIF89a" + struct.pack("<HH", res.w, res.h) + b"\x70\x00\x00"
         if loop is not None:
             head += b"\x21\xFF\x0BNETSCAPE2.0\x03\x01" + struct.pack("<H", int(loop)) + b"\x00"
         with self._lock:
