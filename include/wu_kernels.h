@@ -779,6 +779,22 @@ int wu_knn_radii(const float* x, int ldx, int n, int D, int k, int col_splits, v
 int wu_prdc_counts(const float* x, int ldx, int n1, const double* radii_x, const float* y, int ldy, int n2, const double* radii_y, int D,
                    void* workspace, unsigned* A, unsigned* B, unsigned* C, void* stream);
 
+/* ---- Top-k nearest bank rows of every query row (wu/retrieval.py): which rows of a bank a row is closest to, and how close ------------------
+ * d2 as above, formed as wu_knn_radii forms it.  For query row i, dist2[i*k + j] / index[i*k + j], j < k, are the k smallest pairs
+ * (d2(q_i, b_c), c) over the bank columns c < nb in the lexicographic order: the smaller d2 first, on equal d2 the smaller c.  A total
+ * order, so the result does not depend on col_splits or on the order workgroups finish in; no floating-point atomics: the same inputs give
+ * the same bits.  self_offset >= 0 says that query row i IS bank row self_offset + i (the queries are a chunk of the bank, or the whole of
+ * it at 0): that one column is skipped.  self_offset = -1: no column is skipped.
+ * 64 x 64 tiles of <q, b> on the fp64 matrix cores, grid (query row tiles, col_splits); each (row, split) keeps its k best pairs, a finish
+ * launch merges the splits.  col_splits = 0 lets the library choose as wu_knn_radii does; 1..1024 forces that many.  No distance matrix and
+ * no tile of one reaches global memory.  workspace: wu_nn_workspace_bytes(nq, nb, k, col_splits) bytes, aligned to 8 (0 for arguments out of
+ * range; pure host); ws_bytes is what the caller holds, a short one is refused.  Stream-ordered, caller-owned buffers, no allocation, no
+ * synchronisation.  1 <= k <= 16, 1 <= nq <= 2^21, k <= nb <= 2^21 (k + 1 <= nb and self_offset + nq <= nb with self_offset >= 0),
+ * ld >= D >= 1.  Non-finite features give meaningless neighbours, never an access outside a buffer. */
+size_t wu_nn_workspace_bytes(int nq, int nb, int k, int col_splits);
+int wu_nn_topk(const float* q, int ldq, int nq, const float* b, int ldb, int nb, int D, int k, int self_offset, int col_splits, void* ws,
+               size_t ws_bytes, double* dist2, int* index, void* stream);
+
 /* ---- Rank-aware Frechet distance on feature rows (wu/frechet.py): Tr sqrt(Sigma1 Sigma2) = ||A B^T||_* / sqrt((n1 - 1)(n2 - 1)) ------------
  * A, B are the centred rows of x1 (n1 x D fp32, row stride ld1) and x2 (n2 x D, ld2); A B^T is the double-centred cross-Gram matrix of the
  * raw rows, and its singular values come from a one-sided (Hestenes) Jacobi iteration: no covariance, no matrix square root, any rank.

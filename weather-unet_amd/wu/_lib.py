@@ -162,6 +162,8 @@ SIGNATURES = {
     "wu_prdc_workspace_bytes": (SZ, [I, I, I, I]),
     "wu_knn_radii": (I, [P, I, I, I, I, I, P, P, P]),
     "wu_prdc_counts": (I, [P, I, I, P, P, I, I, P, I, P, P, P, P, P]),
+    "wu_nn_workspace_bytes": (SZ, [I, I, I, I]),
+    "wu_nn_topk": (I, [P, I, I, P, I, I, I, I, I, I, P, SZ, P, P, P]),
     "wu_fd_ld": (I, [I, I]),
     "wu_fd_workspace_bytes": (SZ, [I, I, I]),
     "wu_fd_cross_gram": (I, [P, I, I, P, I, I, I, P, P]),

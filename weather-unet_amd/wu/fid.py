@@ -21,6 +21,11 @@ covariance and no sqrtm, so it is exact on a few hundred images.  It needs ``fea
 
 ``--prdc`` adds improved precision / recall and density / coverage (wu.prdc: k-NN manifold membership on the same rows, PATH1 the real
 set), which tell a loss of diversity from a loss of fidelity; it needs ``features`` in a ``.npz`` PATH just as ``--kid`` does.
+
+``--nn K`` adds one ``NN:`` line on the rows of PATH2 against the bank of PATH1 (wu.retrieval: each row's K nearest rows of PATH1): the
+median and the smallest nearest distance and, with ``--nn-threshold T``, how many rows lie closer than T to a row of PATH1 -- copies of
+training photographs among generated images, or test photographs whose near-duplicate sits in the training set.  ``--nn-report`` writes
+the per-row answer as JSON.  It needs ``features`` in a ``.npz`` PATH just as ``--kid`` does.
 """
 import argparse
 import os
@@ -288,9 +293,15 @@ def main(argv=None):
                     help="also print improved precision / recall and density / coverage of the second path against the first (the real "
                          "set); a .npz path must then hold 'features'")
     ap.add_argument("--prdc-k", type=int, default=5, help="with --prdc: the k of the k-NN radii (prdc's default 5; Kynkaanniemi et al. use 3)")
+    ap.add_argument("--nn", type=int, default=0, metavar="K",
+                    help="also print, for the rows of the second path, the distance to their nearest rows of the first (wu.retrieval: the "
+                         "K nearest, 1..16; the line gives the median and the smallest nearest distance: leakage and memorisation); a "
+                         ".npz path must then hold 'features'")
+    ap.add_argument("--nn-threshold", type=float, default=None, metavar="T", help="with --nn: also count the rows closer than T to a row of the first path")
+    ap.add_argument("--nn-report", default=None, metavar="OUT.json", help="with --nn: write wu.retrieval.nearest_report's dict here")
     args = ap.parse_args(argv)
     stats, banks = _pass_over_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png,
-                                    args.gpu_entropy, fid=True, rows=args.kid or args.prdc or args.fid_rows)
+                                    args.gpu_entropy, fid=True, rows=args.kid or args.prdc or args.fid_rows or args.nn != 0)
     print(f"FID: {calculate_frechet_distance(*stats[0], *stats[1])}")
     if args.fid_rows:
         from .frechet import frechet_distance
@@ -304,6 +315,15 @@ def main(argv=None):
         from .prdc import precision_recall_density_coverage
         m = precision_recall_density_coverage(*banks, k=args.prdc_k)
         print(f"PRDC: precision {m.precision} recall {m.recall} density {m.density} coverage {m.coverage}")
+    if args.nn:
+        import json
+        from .retrieval import nearest_report, nn_line
+        names = [None if p.endswith(".npz") else [f.name for f in image_files(p)] for p in args.path]
+        rep = nearest_report(banks[1], banks[0], threshold=args.nn_threshold, query_names=names[1], bank_names=names[0], k=args.nn)
+        print(nn_line(rep))
+        if args.nn_report:
+            with open(args.nn_report, "w") as fh:
+                json.dump(rep, fh)
     return 0
 
 
