@@ -601,6 +601,28 @@ size_t wu_png_enc_out_stride(int Hmax, int Wmax);
 int wu_png_enc_encode(const void* src, int dtype, long long sn, long long sc, long long sy, long long sx, const void* desc_dev,
                       void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int N, int Hmax, int Wmax,
                       void* stream);
+/* The same encoder with its options; flags == 0 is wu_png_enc_encode: same bytes, same workspace, same three launches.
+ *   WU_PNG_ENC_LZ77  two more launches per batch (match-and-parse, coding) between deflate and frame.  Per segment, nothing crossing a
+ *                    segment: the hash of the three bytes at p is ((b0 | b1 << 8 | b2 << 16) * 0x9E3779B1) >> 19; the segment is walked in
+ *                    blocks of 64 positions, every position of a block reading the head table before the block is inserted (the largest
+ *                    position of a hash stays), so the head candidate of p is the nearest position with its hash in front of its block.
+ *                    Candidates in this order: distances 1, 3, rowstride - 3, rowstride, rowstride + 3 (rowstride = 1 + 3 w), the head
+ *                    candidate; those outside [1, p] are skipped; each is extended to at most min(258, n - p) bytes; the longest wins, a
+ *                    tie goes to the earlier candidate, under 3 bytes is no match; a match is dropped where the one found at the next
+ *                    position is longer.  Greedy parse from position 0.  One dynamic block:
+ *                    both codes limited to 15 bits, HLIT / HDIST trimmed to the last used code, one distance code of length 1 where
+ *                    fewer than two are in use.  The block replaces the stored / literal-only one only where it is strictly smaller, so
+ *                    no file is larger than wu_png_enc_encode's and wu_png_enc_out_stride stays the worst case.  Integer atomics only:
+ *                    the bytes do not depend on scheduling.  Restated in tests/_png_lz_ref.py.
+ * The workspace of the options is larger (one 32-bit word per filtered byte): wu_png_enc_workspace_bytes_ex, 0 for a bad shape or
+ * unknown flags; with flags == 0 it is wu_png_enc_workspace_bytes.  Word 3 of a segment's info in the workspace tells its block:
+ * 0 literal-only, 1 stored, 2 LZ77 (wu_png_enc_seginfo_offset gives where the N * segments * 4 words start). */
+#define WU_PNG_ENC_LZ77 1
+size_t wu_png_enc_workspace_bytes_ex(int N, int Hmax, int Wmax, int flags);
+size_t wu_png_enc_seginfo_offset(int N, int Hmax, int Wmax);
+int wu_png_enc_encode_ex(const void* src, int dtype, long long sn, long long sc, long long sy, long long sx, const void* desc_dev,
+                         void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes, int* result_dev, int N, int Hmax, int Wmax,
+                         int flags, void* stream);
 
 /* ---- image grids and tables (torchvision.utils.make_grid in front of the writers above) ------------------------------------------------
  * Every multi-image output of the reference is make_grid(..., normalize=True, scale_each=True) of the pinned torchvision (< 0.4):

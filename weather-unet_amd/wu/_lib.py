@@ -131,6 +131,9 @@ SIGNATURES = {
     "wu_png_enc_workspace_bytes": (SZ, [I, I, I]),
     "wu_png_enc_out_stride": (SZ, [I, I]),
     "wu_png_enc_encode": (I, [P, I, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, P, SZ, P, SZ, P, I, I, I, P]),
+    "wu_png_enc_workspace_bytes_ex": (SZ, [I, I, I, I]),
+    "wu_png_enc_seginfo_offset": (SZ, [I, I, I]),
+    "wu_png_enc_encode_ex": (I, [P, I, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, P, P, SZ, P, SZ, P, I, I, I, I, P]),
     "wu_gif_enc_segment_pixels": (SZ, []),
     "wu_gif_enc_workspace_bytes": (SZ, [I, I, I]),
     "wu_gif_enc_block_stride": (SZ, [I, I]),

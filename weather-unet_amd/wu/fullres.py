@@ -1,7 +1,7 @@
 """Full-resolution transfer from the command line: every file under every class (or every row of a signal file), written at the
 photograph's own size (``wu.infer_driver.fullres_sweep_to_dir``).
 
-    python -m wu.fullres --checkpoint CKPT --out DIR --classes sunny,cloudy,rain [--size S] [--r R] [--eps E] [--png] FILES...
+    python -m wu.fullres --checkpoint CKPT --out DIR --classes sunny,cloudy,rain [--size S] [--r R] [--eps E] [--png | --png-lz77] FILES...
     python -m wu.fullres --checkpoint CKPT --out DIR --signals FILE.npy [...] FILES...
 
 ``--r`` / ``--eps``: the guided filter's window radius (low-resolution pixels) and regulariser (``wu.guided``); the defaults are untuned."""
@@ -21,6 +21,8 @@ def main(argv=None):
     ap.add_argument("--r", type=int, default=4, help="guided filter radius in low-resolution pixels (untuned default)")
     ap.add_argument("--eps", type=float, default=1e-3, help="guided filter regulariser (untuned default)")
     ap.add_argument("--png", action="store_true", help="write lossless .png files (GPU encoder) instead of .jpg")
+    ap.add_argument("--png-lz77", action="store_true", help="--png with LZ77 matching: smaller files where skies clip or ramps are smooth, "
+                    "never larger ones; more GPU time per file")
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("files", nargs="+")
@@ -45,9 +47,10 @@ def main(argv=None):
     D.load_checkpoint(args.checkpoint, inference=net)
     net = net.to(args.device).eval()
     png = None
+    args.png = args.png or args.png_lz77
     if args.png:
         from .png_enc import GPUPngEncoder
-        png = GPUPngEncoder(device=args.device)
+        png = GPUPngEncoder(device=args.device, matching="lz77" if args.png_lz77 else "none")
     with torch.cuda.device(args.device):
         written = D.fullres_sweep_to_dir(net, args.files, labels, class_names, args.out, args.size, ".png" if args.png else ".jpg",
                                          png_encoder=png, rows=rows, row_names=names, upsampler=GuidedUpsampler(args.r, args.eps))
