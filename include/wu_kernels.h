@@ -1024,6 +1024,42 @@ int wu_guided_coeffs(const float* guide, long long gs_n, long long gs_c, long lo
 int wu_guided_apply(const double* coeffs, int N, int R, int hl, int wl, const unsigned char* photos, int Hmax, int Wmax,
                     const int* sizes_host, const int* sizes_dev, unsigned char* out_u8, float* out_f32, void* stream);
 
+/* ---- Antialiased resampling in front of the metrics (wu/resample.py; csrc/resample.hip) ------------------------------------------------
+ * Pillow's ImagingResample (libImaging/Resample.c: horizontal pass, rounded intermediate, vertical pass; a pass between equal sizes is
+ * skipped) on a ragged batch, ONE launch, no intermediate image in global memory; tests/_resample_ref.py restates the arithmetic.
+ * Bit-identical to Image.resize on RGB uint8 (8-bit mode: 22-bit fixed-point coefficients, uint8 intermediate) and to Image.resize
+ * on each channel as a mode 'F' image (float mode: float64 sums in ascending source order, float32 intermediate, no clipping).
+ *   src        src_kind 0: uint8, 1: float32, 2: bf16; image n's sample (y, x, c) is element src_off + y s_row + x s_col + c s_ch.  A float
+ *              source is mapped to 0..255 in float32 as x * 255.0f, or with WU_RESAMPLE_RANGE_PM1 as x * 127.5f + 127.5f (two roundings);
+ *              in 8-bit mode it is then clamped to [0, 255] and truncated (wu.infer_driver.to_uint8).
+ *   workspace  N descriptors of wu_resample_desc_bytes() (= 64) bytes, then the tables; `descs_host` is the same N descriptors in host
+ *              memory, checked before anything touches the device:
+ *                  int64 src_off, s_row, s_col, s_ch; int32 src_h, src_w, hb, hk, vb, vk, kx, ky;
+ *              hb / vb: byte offsets in the workspace of int32 bounds[out][2] = {first source index, count}; hk: coefficients [kx][Wout]
+ *              (tap-major), vk: [Hout][ky]; float64 in float mode, int32 (normalize_coeffs_8bpc) in 8-bit mode.  kx == 0 / ky == 0: that
+ *              pass is skipped (src_w == Wout / src_h == Hout).  The caller builds the tables (precompute_coeffs) on the host.
+ *   flags      WU_RESAMPLE_MODE_U8 | epilogue << 4 | band << 8 | WU_RESAMPLE_NORMALIZE | WU_RESAMPLE_RANGE_PM1.  band: output rows per
+ *              workgroup, 1..wu_resample_max_band(), 0 = the default; every band height gives the same bits.
+ *   epilogues  WU_RESAMPLE_OUT_NHWC_U8 (N, Hout, Wout, 3) uint8, 8-bit mode only; WU_RESAMPLE_OUT_RAW (N, 3, Hout, Wout) fp32, Pillow's
+ *              value itself; _UNIT: clip(v, 0, 255) / 255.0f; _NORM: (unit - 0.5f) / 0.5f; _INCEPTION: unit, then with
+ *              WU_RESAMPLE_NORMALIZE (float)(2.0 * unit - 1.0), into (N, Hout, Wout, cpad) of dst_dtype with pixel stride ldy, channels
+ *              3..cpad-1 zero -- what wu_inception_input writes for the same (0, 1) image of the network's size.
+ * Hout, Wout <= 1024; N * Hout * Wout < 2^31; a source row that takes a horizontal pass must fit 64 KiB of LDS (21845 pixels as bytes,
+ * 5461 as float32: a float source in float mode). */
+#define WU_RESAMPLE_MODE_U8 1
+#define WU_RESAMPLE_OUT_NHWC_U8 0
+#define WU_RESAMPLE_OUT_RAW 1
+#define WU_RESAMPLE_OUT_UNIT 2
+#define WU_RESAMPLE_OUT_NORM 3
+#define WU_RESAMPLE_OUT_INCEPTION 4
+#define WU_RESAMPLE_NORMALIZE (1 << 16)
+#define WU_RESAMPLE_RANGE_PM1 (1 << 17)
+size_t wu_resample_desc_bytes(void);
+int wu_resample_max_band(void);
+size_t wu_resample_workspace_bytes(int N, size_t table_bytes);       /* 0 for N <= 0 */
+int wu_resample(const void* src, int src_kind, const void* descs_host, const void* workspace, size_t workspace_bytes, int N, int Hout,
+                int Wout, void* dst, int ldy, int cpad, int dst_dtype, int flags, void* stream);
+
 /* ---- instrumentation (bench.py roofline leg) -------------------------------------------------
  * While enabled, the launchers of the kernel families in `family_mask` (bit f = family f) bracket each
  * launch with hipEvents on the launch stream (events come from a pool created by wu_prof_begin; nothing

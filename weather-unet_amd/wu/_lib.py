@@ -197,6 +197,10 @@ SIGNATURES = {
     "wu_guided_coeffs": (I, [P] + [ctypes.c_longlong] * 4 + [c_double, c_double, P] + [ctypes.c_longlong] * 5 + [I, c_double, c_double]
                          + [I] * 5 + [c_double, P, P, P]),
     "wu_guided_apply": (I, [P, I, I, I, I, P, I, I, P, P, P, P, P]),
+    "wu_resample_desc_bytes": (SZ, []),
+    "wu_resample_max_band": (I, []),
+    "wu_resample_workspace_bytes": (SZ, [I, SZ]),
+    "wu_resample": (I, [P, I, P, P, SZ, I, I, I, P, I, I, I, I, P]),
     "wu_prof_begin": (I, [ctypes.c_uint, I]),
     "wu_prof_query": (I, [I, POINTER(c_int), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "wu_prof_end": (I, []),

@@ -16,12 +16,15 @@ def as_rows(f, who):
 
 class FeatureBank:
     """Feature rows kept on the GPU, appended batch by batch.  ``features`` is the (n, D) view of the rows so far, ``n`` their number; the
-    device buffer doubles when it is full.  ``save_npz`` / ``load_npz`` use the key ``features`` (float32)."""
+    device buffer doubles when it is full.  ``save_npz`` / ``load_npz`` use the key ``features`` (float32).  ``resize`` is the rule the
+    images reached the network under (``InceptionV3(resize=...)``); anything but ``"legacy"`` is recorded under the key ``resize``, and a
+    file without that key is legacy."""
 
-    def __init__(self, dim=None):
+    def __init__(self, dim=None, resize="legacy"):
         self.dim = dim
         self.n = 0
         self._buf = None
+        self.resize = resize
 
     def append(self, feats):
         feats = as_rows(feats, "FeatureBank.append")
@@ -50,7 +53,7 @@ class FeatureBank:
         return self._buf[:self.n]
 
     def save_npz(self, path):
-        np.savez(path, features=self.features.cpu().numpy())
+        np.savez(path, features=self.features.cpu().numpy(), **({} if self.resize == "legacy" else {"resize": np.array(self.resize)}))
 
     @classmethod
     def load_npz(cls, path, device="cuda"):
@@ -58,9 +61,10 @@ class FeatureBank:
             if "features" not in f:
                 raise ValueError(f"{path}: no 'features' array (keys {sorted(f.keys())}); KID needs the feature rows, not mu / sigma")
             a = np.ascontiguousarray(f["features"], dtype=np.float32)
+            rule = str(f["resize"]) if "resize" in f else "legacy"
         if a.ndim != 2:
             raise ValueError(f"{path}: 'features' has shape {a.shape}, expected (n, D)")
-        bank = cls(a.shape[1])
+        bank = cls(a.shape[1], rule)
         if a.shape[0]:
             bank.append(torch.from_numpy(a).to(device))
         return bank

@@ -26,6 +26,12 @@ set), which tell a loss of diversity from a loss of fidelity; it needs ``feature
 median and the smallest nearest distance and, with ``--nn-threshold T``, how many rows lie closer than T to a row of PATH1 -- copies of
 training photographs among generated images, or test photographs whose near-duplicate sits in the training set.  ``--nn-report`` writes
 the per-row answer as JSON.  It needs ``features`` in a ``.npz`` PATH just as ``--kid`` does.
+
+``--resize clean`` brings the images to 299 x 299 with Pillow's antialiased bicubic filter on float32 channels, without quantisation
+(wu.resample, float mode; Parmar et al., CVPR 2022), instead of the aliased bilinear interpolation of pytorch-fid (``legacy``, the default),
+and reads directories of MIXED image sizes.  It is the resize rule only: network and weights stay pytorch-fid's, so the numbers are not
+comparable with the statistics files the ``clean-fid`` package publishes.  ``.npz`` files record the rule they were computed under (no key:
+legacy); paths under different rules raise.
 """
 import argparse
 import os
@@ -40,6 +46,8 @@ from .features import FeatureBank, as_rows
 from .inception import InceptionV3, global_avgpool
 from .layout import precision_code, stream_ptr
 
+LEGACY, CLEAN = "legacy", "clean"         # the resize rules of InceptionV3(resize=...)
+
 
 class FIDStatistics:
     """Running mean / covariance of InceptionV3 features (the first requested block of ``model``: pool3 by default).
@@ -52,9 +60,10 @@ class FIDStatistics:
         self.n = 0
         self._sum = self._cross = self._shift = None
 
-    def update(self, images, value_range=(0, 1), features=None):
-        """``features``: a wu.features.FeatureBank that also receives the batch's rows (for the KID)."""
-        feat = self.model(images, value_range=value_range)[0]
+    def update(self, images, value_range=(0, 1), features=None, sizes=None):
+        """``features``: a wu.features.FeatureBank that also receives the batch's rows (for the KID).  ``sizes``: [(h, w)] per image of a
+        padded ragged uint8 batch (a model with ``resize="clean"`` only)."""
+        feat = self.model(images, value_range=value_range)[0] if sizes is None else self.model(images, value_range=value_range, sizes=sizes)[0]
         n, c, h, w = feat.shape
         if h * w != 1 or feat.dtype != torch.float32:
             feat = global_avgpool(feat, precision_code(self.model.precision))
@@ -92,8 +101,25 @@ class FIDStatistics:
         return mu, sigma
 
     def save_npz(self, path):
+        """``mu`` / ``sigma``, and the resize rule under ``resize`` when it is not the legacy one (a file without the key is legacy)."""
         mu, sigma = self.finalize()
-        np.savez(path, mu=mu, sigma=sigma)
+        rule = getattr(self.model, "resize", LEGACY)
+        np.savez(path, mu=mu, sigma=sigma, **({} if rule == LEGACY else {"resize": np.array(rule)}))
+
+
+def npz_resize_rule(path):
+    """The resize rule a statistics / feature file was recorded under: its ``resize`` key, ``"legacy"`` without one."""
+    with np.load(path) as f:
+        return str(f["resize"]) if "resize" in f else LEGACY
+
+
+def check_same_resize(paths, resize):
+    """Raise if the paths were (or would be) evaluated under different resize rules: a directory under ``resize``, a .npz under the
+    rule it records.  Statistics under the aliased and under the antialiased resize differ by more than models do."""
+    rules = [npz_resize_rule(p) if p.endswith(".npz") else resize for p in paths]
+    if len(set(rules)) > 1:
+        raise ValueError("resize rules differ: " + ", ".join(f"{p}: {r}" for p, r in zip(paths, rules)) +
+                         " (statistics recorded under different resize rules are not comparable)")
 
 
 def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
@@ -148,24 +174,50 @@ def image_files(path):
     return sorted(list(p.glob("*.jpg")) + list(p.glob("*.png")))
 
 
-def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False, features=None):
+def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False, features=None, resize=None):
     """(mu, sigma) of a .npz file or of the images in a directory (uint8 batches straight to the GPU).  gpu_decode: read the files
     through wu.jpeg.GPUJpegDecoder instead of the per-file Pillow loop; gpu_decode_png: through wu.png.GPUPngDecoder, which inflates the
     segmented PNGs wu.png_enc writes on the GPU and hands every other file to Pillow -- the same uint8 batch, hence the same statistics.
     gpu_entropy (implies gpu_decode): the JPEG decoder also Huffman-decodes on the GPU (``entropy="device"``).  All off by default.
     features: a wu.features.FeatureBank that also receives every feature row (the KID's input); a .npz must then hold ``features``, and its
-    ``mu`` / ``sigma`` are taken from the file when it has them and computed from the rows when it does not."""
+    ``mu`` / ``sigma`` are taken from the file when it has them and computed from the rows when it does not.
+    resize: the model's rule (``InceptionV3(resize=...)``; None: whatever the model has).  ``"clean"`` reads a directory of MIXED sizes on
+    all three read paths, as padded ragged batches through wu.resample; ``"legacy"`` raises on one, as it always has.  A .npz recorded
+    under another rule than ``resize`` raises."""
     gpu_decode = gpu_decode or gpu_entropy
     if path.endswith(".npz"):
+        if resize is not None and npz_resize_rule(path) != resize:
+            raise ValueError(f"resize rules differ: {path} was recorded under {npz_resize_rule(path)!r}, not {resize!r}")
         if features is None:
             with np.load(path) as f:
                 return f["mu"][:], f["sigma"][:]
         return _npz_statistics_and_features(path, features)
+    rule = getattr(model, "resize", LEGACY)
+    if resize is not None and resize != rule:
+        raise ValueError(f"statistics_of_path: resize={resize!r}, but the model was built with resize={rule!r}")
     from PIL import Image
     files = image_files(path)
     if not files:
         raise RuntimeError(f"no .jpg / .png images in {path}")
     stats = FIDStatistics(model)
+    if features is not None and rule != LEGACY:
+        features.resize = rule
+    if rule == CLEAN:
+        from .resample import read_batches
+        dec = None
+        if gpu_decode_png:
+            from . import png
+            dec = png.GPUPngDecoder()
+        elif gpu_decode:
+            from .jpeg import GPUJpegDecoder
+            dec = GPUJpegDecoder(entropy="device" if gpu_entropy else "host")
+        try:
+            for batch, sizes in read_batches(files, batch_size, dec):
+                stats.update(batch, features=features, sizes=sizes)
+        finally:
+            if dec is not None:
+                dec.close()
+        return stats.finalize()
     if gpu_decode or gpu_decode_png:
         if gpu_decode_png:
             from . import png
@@ -190,6 +242,7 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png
 
 def _npz_statistics_and_features(path, features):
     bank = FeatureBank.load_npz(path)
+    features.resize = bank.resize
     if bank.n:
         features.append(bank.features)
     with np.load(path) as f:
@@ -200,67 +253,79 @@ def _npz_statistics_and_features(path, features):
     return stats.finalize()
 
 
-def _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid, rows):
+def _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid, rows, resize=LEGACY):
     """What every entry point below shares: the path check, the model loaded once (not at all for .npz files alone) and ONE pass over each
     path.  Returns (stats, banks), a list per path each: (mu, sigma) when ``fid`` and a FeatureBank of the feature rows when ``rows``, None
     otherwise.  Without ``rows`` a .npz is read for ``mu`` / ``sigma`` only; with ``rows`` it must hold ``features``, and without ``fid``
-    it needs nothing else."""
+    it needs nothing else.  ``resize``: the rule directories are read under (``InceptionV3(resize=...)``); paths under different rules --
+    a .npz records its own -- raise before anything is computed."""
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError(f"Invalid path: {p}")
+    if resize not in (LEGACY, CLEAN):
+        raise ValueError(f"resize must be {LEGACY!r} or {CLEAN!r}, got {resize!r}")
+    check_same_resize(paths, resize)
     model = None
     if not all(p.endswith(".npz") for p in paths):
-        model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], precision=precision)
+        model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], precision=precision, resize=resize)
         model.load_state_dict(torch.load(weights, map_location="cpu"))
     stats, banks = [], []
     for p in paths:
         bank = FeatureBank() if rows else None
         if rows and not fid and p.endswith(".npz"):
-            bank.append(FeatureBank.load_npz(p).features)
+            loaded = FeatureBank.load_npz(p)
+            bank.append(loaded.features)
+            bank.resize = loaded.resize
             st = None
         else:
-            st = statistics_of_path(p, model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=bank)
+            st = statistics_of_path(p, model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=bank,
+                                    resize=None if p.endswith(".npz") else resize)      # a .npz keeps its own rule (checked above)
         stats.append(st if fid else None)
         banks.append(bank)
     return stats, banks
 
 
 def calculate_fid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                              gpu_entropy=False):
-    stats, _ = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=True, rows=False)
+                              gpu_entropy=False, resize=LEGACY):
+    stats, _ = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=True, rows=False,
+                                resize=resize)
     return calculate_frechet_distance(*stats[0], *stats[1])
 
 
 def calculate_fid_and_banks_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                                        gpu_entropy=False):
+                                        gpu_entropy=False, resize=LEGACY):
     """(fid, (bank1, bank2)) from ONE pass over each path: the feature rows feed the moment accumulators and a FeatureBank each, which
     wu.kid.kernel_inception_distance and wu.prdc.precision_recall_density_coverage then share (``--kid`` / ``--prdc``)."""
-    stats, banks = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=True, rows=True)
+    stats, banks = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=True, rows=True,
+                                    resize=resize)
     return calculate_frechet_distance(*stats[0], *stats[1]), tuple(banks)
 
 
 def calculate_fid_and_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                                      gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
+                                      gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020, resize=LEGACY):
     """(fid, (kid_mean, kid_std)) from ONE pass over each path."""
     from .kid import kernel_inception_distance
-    fid, banks = calculate_fid_and_banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy)
+    fid, banks = calculate_fid_and_banks_given_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy,
+                                                     resize=resize)
     return fid, kernel_inception_distance(*banks, num_subsets=num_subsets, subset_size=subset_size, seed=seed)
 
 
 def calculate_kid_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                              gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020):
+                              gpu_entropy=False, num_subsets=100, subset_size=1000, seed=2020, resize=LEGACY):
     """(mean, std) of the Kernel Inception Distance between two image directories / .npz files holding ``features``."""
     from .kid import kernel_inception_distance
-    _, banks = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=False, rows=True)
+    _, banks = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=False, rows=True,
+                                resize=resize)
     return kernel_inception_distance(*banks, num_subsets=num_subsets, subset_size=subset_size, seed=seed)
 
 
 def calculate_prdc_given_paths(paths, weights, batch_size=50, dims=2048, precision="fp32", gpu_decode=False, gpu_decode_png=False,
-                               gpu_entropy=False, k=5):
+                               gpu_entropy=False, k=5, resize=LEGACY):
     """wu.prdc.PRDC(precision, recall, density, coverage) of paths[1] (the generated set) against paths[0] (the real set): two image
     directories / .npz files holding ``features``, one pass over each."""
     from .prdc import precision_recall_density_coverage
-    _, banks = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=False, rows=True)
+    _, banks = _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid=False, rows=True,
+                                resize=resize)
     return precision_recall_density_coverage(*banks, k=k)
 
 
@@ -278,6 +343,11 @@ def main(argv=None):
                          "coefficients goes over the link")
     ap.add_argument("--gpu-decode-png", action="store_true",
                     help="decode segmented PNG files (what wu.png_enc writes) with wu.png.GPUPngDecoder (HIP kernels); other files go to Pillow")
+    ap.add_argument("--resize", default=LEGACY, choices=[LEGACY, CLEAN],
+                    help="how images reach 299 x 299: 'legacy' is pytorch-fid's bilinear interpolation without antialiasing; 'clean' is "
+                         "Pillow's antialiased bicubic filter on float32 channels without quantisation (wu.resample; Parmar et al. 2022), "
+                         "which also reads directories of mixed image sizes.  The rule only: network and weights stay pytorch-fid's, so the "
+                         "numbers are not comparable with the statistics files the clean-fid package publishes")
     ap.add_argument("--kid", action="store_true",
                     help="also print the Kernel Inception Distance (mean and standard deviation over random subsets of the feature rows); "
                          "a .npz path must then hold 'features'")
@@ -301,7 +371,7 @@ def main(argv=None):
     ap.add_argument("--nn-report", default=None, metavar="OUT.json", help="with --nn: write wu.retrieval.nearest_report's dict here")
     args = ap.parse_args(argv)
     stats, banks = _pass_over_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png,
-                                    args.gpu_entropy, fid=True, rows=args.kid or args.prdc or args.fid_rows or args.nn != 0)
+                                    args.gpu_entropy, fid=True, rows=args.kid or args.prdc or args.fid_rows or args.nn != 0, resize=args.resize)
     print(f"FID: {calculate_frechet_distance(*stats[0], *stats[1])}")
     if args.fid_rows:
         from .frechet import frechet_distance

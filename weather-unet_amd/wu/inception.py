@@ -157,8 +157,14 @@ class InceptionV3(nn.Module):
     BLOCK_INDEX_BY_DIM = {64: 0, 192: 1, 768: 2, 2048: 3}
 
     def __init__(self, output_blocks=(DEFAULT_BLOCK_INDEX,), resize_input=True, normalize_input=True, requires_grad=False,
-                 use_fid_inception=True, precision="fp32"):
+                 use_fid_inception=True, precision="fp32", resize="legacy"):
         super().__init__()
+        if resize not in ("legacy", "clean"):
+            raise ValueError(f"resize must be 'legacy' or 'clean', got {resize!r}")
+        if resize == "clean" and not resize_input:
+            raise ValueError("resize='clean' is a resize rule: it needs resize_input=True")
+        self.resize = resize
+        self._resampler = None
         if requires_grad:
             raise ValueError("InceptionV3 here is forward-only (evaluation): requires_grad=True is not supported")
         self.output_blocks = sorted(output_blocks)
@@ -278,11 +284,20 @@ class InceptionV3(nn.Module):
         if self.last_needed_block >= 3:
             need3(h, w, "Mixed_7a")
 
-    def prepare(self, images, value_range=(0, 1)):
+    def prepare(self, images, value_range=(0, 1), sizes=None):
         """Images -> the NHWC network input (N, 16, 299, 299) [or the input size without resize_input] in the storage dtype.
-        ``images``: (N, 3, H, W) float32 (values in ``value_range``: (0, 1) or (-1, 1)) or (N, H, W, 3) uint8 (wu.infer_driver.to_uint8)."""
+        ``images``: (N, 3, H, W) float32 (values in ``value_range``: (0, 1) or (-1, 1)) or (N, H, W, 3) uint8 (wu.infer_driver.to_uint8).
+        ``resize="clean"``: the resize is Pillow's antialiased bicubic filter on float32 channels (wu.resample, float mode) instead of the
+        aliased bilinear one; ``images`` may then be a padded ragged uint8 batch (N, Hmax, Wmax, 3) with ``sizes`` = [(h, w)] per image."""
         require_cuda(images, "InceptionV3")
         code = precision_code(self.precision)
+        if self.resize == "clean":
+            if self._resampler is None:
+                from .resample import GPUResampler
+                self._resampler = GPUResampler(RESIZE, "bicubic", "f32", "unit")
+            return self._resampler.inception_input(images, sizes, value_range, CIN0, code, self.normalize_input)
+        if sizes is not None:
+            raise ValueError("InceptionV3: sizes (a ragged batch) need resize='clean'; the legacy resize reads one size per batch")
         if images.dtype == torch.uint8:
             if images.dim() != 4 or images.shape[3] != 3:
                 raise ValueError(f"InceptionV3: uint8 images must be (N, H, W, 3), got {tuple(images.shape)}")
@@ -312,13 +327,13 @@ class InceptionV3(nn.Module):
                   x.data_ptr(), CIN0, ho, wo, CIN0, code, stream_ptr())
         return x
 
-    def forward(self, images, value_range=(0, 1)):
-        x = self.prepare(images, value_range)
+    def forward(self, images, value_range=(0, 1), sizes=None):
+        x = self.prepare(images, value_range, sizes)
         return self._blocks(x, self.output_blocks, self.last_needed_block)
 
-    def logits(self, images, value_range=(0, 1)):
+    def logits(self, images, value_range=(0, 1), sizes=None):
         """(N, num_classes) fp32 logits: pool3 features through ``fc`` (eval mode: no dropout)."""
-        x = self.prepare(images, value_range)
+        x = self.prepare(images, value_range, sizes)
         feat = self._blocks(x, [3], 3)[0]
         P = self.plan(feat.device)
         n = feat.shape[0]

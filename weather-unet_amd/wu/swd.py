@@ -6,7 +6,7 @@ Pixels only: no pretrained network, no feature extractor.
     d = descriptors(images, positions)                  # per level, (N * P, 147) float32 CUDA
     dn, mu, sigma = normalize(d[0])
     w = sliced_wasserstein(dn_a, dn_b, dirs)            # (ndirs,) float64 CUDA
-    python -m wu.swd DIR_A DIR_B [--size S] [--patches 128] [--repeats 4] [--dirs 128] [--seed 0] [--gpu-decode]
+    python -m wu.swd DIR_A DIR_B [--size S [--filter bicubic]] [--patches 128] [--repeats 4] [--dirs 128] [--seed 0] [--gpu-decode]
 
 Semantics, in full (tests/_swd_ref.py restates them in numpy).  All pyramid arithmetic in float64, every operation rounded on its own.
 
@@ -264,13 +264,25 @@ def swd(images_a, images_b, P=128, repeats=4, dirs_per_repeat=128, seed=0, value
 # ----------------------------------------------------------------------------------------------
 # command line
 # ----------------------------------------------------------------------------------------------
-def _read_dir(files, size, gpu_decode, device, batch_size=64):
-    """The files as uint8 NHWC batches (read through their strides), or as (N, 3, S, S) float32 in [-1, 1] with ``size``."""
+def _read_dir(files, size, gpu_decode, device, batch_size=64, filter=None):
+    """The files as uint8 NHWC batches (read through their strides), or as (N, 3, S, S) float32 in [-1, 1] with ``size``.  ``filter``
+    (with ``size``): resize with that Pillow filter in 8-bit mode through wu.resample instead of the training pipeline's bilinear one."""
     from PIL import Image
     dec = pipe = None
+    if filter is not None and not size:
+        raise ValueError("--filter chooses how --size resizes: give --size")
     if gpu_decode:
         from .jpeg import GPUJpegDecoder
         dec = GPUJpegDecoder()
+    if filter is not None:
+        from .resample import resize_files
+        try:
+            for x in resize_files(files, size, filter, "u8", "nchw", batch_size, dec, device):
+                yield x, (-1, 1)
+        finally:
+            if dec is not None:
+                dec.close()
+        return
     if size:
         from .input_pipeline import GPUInputPipeline
         pipe = GPUInputPipeline(size, train=False)
@@ -298,10 +310,12 @@ def _read_dir(files, size, gpu_decode, device, batch_size=64):
             dec.close()
 
 
-def swd_of_dirs(dir_a, dir_b, size=None, P=128, repeats=4, dirs_per_repeat=128, seed=0, gpu_decode=False, device="cuda:0", log=print):
+def swd_of_dirs(dir_a, dir_b, size=None, P=128, repeats=4, dirs_per_repeat=128, seed=0, gpu_decode=False, device="cuda:0", log=print,
+                filter=None):
     """SWDResult of the .jpg / .png files of two directories, and the number of images used per set.  Images are resized (through
     ``wu.input_pipeline``) only with ``size``; otherwise mixed sizes are an error.  Directories of unequal count: a random subset of the
-    larger one, drawn from ``seed``, and a line through ``log`` that says so."""
+    larger one, drawn from ``seed``, and a line through ``log`` that says so.  ``filter`` (box, bilinear, bicubic, lanczos; with ``size``):
+    resize with that Pillow filter in 8-bit mode through ``wu.resample`` instead."""
     from .evaluate import SlicedWasserstein
     from .fid import image_files
     fa, fb = image_files(dir_a), image_files(dir_b)
@@ -318,7 +332,8 @@ def swd_of_dirs(dir_a, dir_b, size=None, P=128, repeats=4, dirs_per_repeat=128, 
         else:
             fb = [fb[i] for i in keep]
     acc = SlicedWasserstein(P=P, repeats=repeats, dirs_per_repeat=dirs_per_repeat, seed=seed)
-    for (xa, ra), (xb, rb) in zip(_read_dir(fa, size, gpu_decode, device), _read_dir(fb, size, gpu_decode, device)):
+    for (xa, ra), (xb, rb) in zip(_read_dir(fa, size, gpu_decode, device, filter=filter),
+                                      _read_dir(fb, size, gpu_decode, device, filter=filter)):
         acc.value_range = ra
         acc.update(xa, xb)
     return acc.compute(), n
@@ -336,8 +351,13 @@ def main(argv=None):
     ap.add_argument("--dirs", type=int, default=128, help="directions per repeat")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gpu-decode", action="store_true", help="read the JPEG files through wu.jpeg.GPUJpegDecoder")
+    ap.add_argument("--filter", default=None, choices=["box", "bilinear", "bicubic", "lanczos"],
+                    help="with --size: resize with this Pillow filter (Image.resize, 8-bit) through wu.resample; absent: the training "
+                         "pipeline's bilinear resize, as before")
     args = ap.parse_args(argv)
-    r, n = swd_of_dirs(args.dir_a, args.dir_b, args.size, args.patches, args.repeats, args.dirs, args.seed, args.gpu_decode)
+    if args.filter is not None and not args.size:
+        ap.error("--filter chooses how --size resizes: give --size")
+    r, n = swd_of_dirs(args.dir_a, args.dir_b, args.size, args.patches, args.repeats, args.dirs, args.seed, args.gpu_decode, filter=args.filter)
     for l, v in enumerate(r.levels):
         print(f"SWD x 1e3, level {l}: {v:.4f}")
     print(f"SWD x 1e3, mean: {r.mean:.4f}")
