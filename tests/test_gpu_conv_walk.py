@@ -447,7 +447,12 @@ def test_conv3x3_wgrad_v2_tile_loop_is_exact(case):
 @pytest.mark.parametrize("gated", [False, True])
 def test_conv3x3_wgrad_generic_is_exact(shape, gated):
     """The generic weight gradient (W % 32 != 0, or gated in the kernel by the stored activation y): the path of ten of the thirteen
-    weight gradients at 224 x 224.  Whole chip and a forced grid of 5."""
+    weight gradients at 224 x 224.  Run twice, the second time with option 10 = 5: the generic plan never reads that option (its split
+    count is ceil(512 / channel blocks) capped by the tile count), so the second run repeats the first -- it shows that a forced grid
+    changes nothing here, it is NOT a walk.  All three shapes give one tile per split (asserted from the plan mirror in
+    tests/test_wgrad_ref_cpu.py).  The tile loop of conv3x3_wgrad_kernel<bf16_t,1,256> is walked by test_unet_layers_at_224_are_exact
+    (512 -> 512 at 28 x 28: 8 tiles per split), that of the other three instances by the 45 x 79 cases of tests/test_gpu_wgrad_exact.py
+    (3 to 7 tiles per split, uneven)."""
     n, cin, cout, h, w = shape
     assert gated or not _wgrad_v2_eligible(h, w, cin, cout)
     x, gy, y, dw_ref, db_ref = _wgrad_reference(shape, 300, gated)
