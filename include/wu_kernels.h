@@ -817,6 +817,55 @@ size_t wu_nn_workspace_bytes(int nq, int nb, int k, int col_splits);
 int wu_nn_topk(const float* q, int ldq, int nq, const float* b, int ldb, int nb, int D, int k, int self_offset, int col_splits, void* ws,
                size_t ws_bytes, double* dist2, int* index, void* stream);
 
+/* ---- Every pair under a radius (wu/retrieval.py: radius_join, leak_mask, duplicate_groups): the clean split a top-k search cannot give -------
+ * d2 as above, the same bits as wu_nn_topk and wu_knn_radii form.  The pair (i, c), i < nq, c < nb, is a MEMBER when
+ *     d2(q_i, b_c) <= radius2                                  (`<=`, as wu_prdc_counts decides it),
+ *     c != self_offset + i        when self_offset >= 0        (query row i IS bank row self_offset + i, as in wu_nn_topk),
+ *     c >  self_offset + i        when upper_only != 0         (needs self_offset >= 0: each unordered pair of a self-join once).
+ * The result is CSR: row_ptr (nq + 1 int64, row_ptr[0] = 0), and for row i at positions row_ptr[i] .. row_ptr[i + 1] - 1 the member columns
+ * col, ascending, with dist2 beside them.  Two passes over the same 64 x 64 fp64 matrix-core tiles, grid (query row tiles, col_splits):
+ *   wu_nn_radius_count   norms, then per (row, split) the number of members and per tile one byte that says whether it holds any, then ONE
+ *                        workgroup turns the counts into exclusive int64 offsets (kept in the workspace, as the bytes are) and row_ptr.  The caller reads row_ptr[nq] (8 bytes: the one synchronisation) and sizes
+ *                        col / dist2 with it.
+ *   wu_nn_radius_fill    the SAME arguments and the workspace as wu_nn_radius_count left it, plus row_ptr and the capacity of col / dist2
+ *                        in entries: recomputes the tiles that hold a member and writes each row's members from its (row, split) offset.  A
+ *                        workgroup whose rows have no member in its split returns before its first tile.  capacity must be >= row_ptr[nq] (the caller, who
+ *                        has read it, checks; the kernel stores only inside min(row_ptr[i + 1], capacity), so a short buffer loses entries
+ *                        and is never overrun).  capacity == 0 launches nothing and accepts NULL col / dist2.
+ * One (row, split) slot is written by one thread, columns ascending, so the bytes do not depend on col_splits or on the order workgroups
+ * finish in; nothing crosses workgroups through an atomic and no workgroup waits on another.  col_splits = 0 lets the library choose: among
+ * 1 .. max(768 / row tiles, 8) splits (at most one per column tile) the one whose row tiles x splits best fill whole rounds of the 768
+ * workgroups resident at once on a 256-CU part, the fewer on a tie; 1..1024 forces that many.  No distance matrix and no tile of one
+ * reaches global memory.  workspace: wu_nn_radius_workspace_bytes(nq, nb, col_splits) bytes, aligned to 8
+ * (0 for arguments out of range; pure host); ws_bytes is what the caller holds, a short one is refused.  Stream-ordered, caller-owned
+ * buffers, no allocation, no synchronisation.  radius2 finite and >= 0 (NaN, inf and negative values are refused), 1 <= nq, nb <= 2^21,
+ * self_offset = -1 or 0 <= self_offset <= nb - nq, ld >= D >= 1.  Non-finite features give a meaningless result, never an access outside a
+ * buffer. */
+size_t wu_nn_radius_workspace_bytes(int nq, int nb, int col_splits);
+int wu_nn_radius_count(const float* q, int ldq, int nq, const float* b, int ldb, int nb, int D, double radius2, int self_offset,
+                       int upper_only, int col_splits, void* ws, size_t ws_bytes, long long* row_ptr, void* stream);
+int wu_nn_radius_fill(const float* q, int ldq, int nq, const float* b, int ldb, int nb, int D, double radius2, int self_offset,
+                      int upper_only, int col_splits, void* ws, size_t ws_bytes, const long long* row_ptr, long long capacity, int* col,
+                      double* dist2, void* stream);
+
+/* ---- Per-row realism and rarity against a bank's k-NN balls (wu/retrieval.py: ball_scores) ----------------------------------------------------
+ * r2 (nb doubles) are the bank's squared k-NN radii, what wu_knn_radii writes.  Per query row i, over the columns j < nb that self_offset
+ * leaves in (as above), with d2_ij = d2(q_i, b_j):
+ *     count[i]         = #{ j : d2_ij <= r2[j] }                      without a self_offset wu_prdc_counts' B[i], bit for bit;
+ *     rarity_r2[i]     = min{ r2[j] : d2_ij <= r2[j] }, +inf when the row lies in no ball (Han et al. 2022: the smallest ball that holds it);
+ *     rarity_index[i]  = its column, the smaller j on equal radii, -1 when there is none;
+ *     realism_*[i]     : the maximiser over j of rho_ij = r2[j] / d2_ij, ONE IEEE fp64 division per pair, +inf when d2_ij == 0 whatever
+ *                        r2[j] is, on equal rho the smaller j: realism_r2[i] = r2[j], realism_d2[i] = d2_ij, realism_index[i] = j.  The
+ *                        realism score of Kynkaanniemi et al. 2019 is sqrt(rho), formed by the caller from the pair.
+ * One walk of the same tiles, grid (query row tiles, col_splits), then a finish launch that merges the splits by the same total-order rules:
+ * the result does not depend on col_splits or on the order workgroups finish in.  col_splits as above.  workspace:
+ * wu_nn_ball_workspace_bytes(nq, nb, col_splits) bytes, aligned to 8 (0 for arguments out of range; pure host).  The limits are the join's,
+ * and nb >= 2 with self_offset >= 0 (a maximiser must exist).  r2 is expected finite and >= 0; other values give meaningless scores. */
+size_t wu_nn_ball_workspace_bytes(int nq, int nb, int col_splits);
+int wu_nn_ball_scores(const float* q, int ldq, int nq, const float* b, int ldb, int nb, int D, const double* r2, int self_offset,
+                      int col_splits, void* ws, size_t ws_bytes, unsigned* count, double* rarity_r2, int* rarity_index, double* realism_r2,
+                      double* realism_d2, int* realism_index, void* stream);
+
 /* ---- Rank-aware Frechet distance on feature rows (wu/frechet.py): Tr sqrt(Sigma1 Sigma2) = ||A B^T||_* / sqrt((n1 - 1)(n2 - 1)) ------------
  * A, B are the centred rows of x1 (n1 x D fp32, row stride ld1) and x2 (n2 x D, ld2); A B^T is the double-centred cross-Gram matrix of the
  * raw rows, and its singular values come from a one-sided (Hestenes) Jacobi iteration: no covariance, no matrix square root, any rank.

@@ -167,6 +167,11 @@ SIGNATURES = {
     "wu_prdc_counts": (I, [P, I, I, P, P, I, I, P, I, P, P, P, P, P]),
     "wu_nn_workspace_bytes": (SZ, [I, I, I, I]),
     "wu_nn_topk": (I, [P, I, I, P, I, I, I, I, I, I, P, SZ, P, P, P]),
+    "wu_nn_radius_workspace_bytes": (SZ, [I, I, I]),
+    "wu_nn_radius_count": (I, [P, I, I, P, I, I, I, c_double, I, I, I, P, SZ, P, P]),
+    "wu_nn_radius_fill": (I, [P, I, I, P, I, I, I, c_double, I, I, I, P, SZ, P, ctypes.c_longlong, P, P, P]),
+    "wu_nn_ball_workspace_bytes": (SZ, [I, I, I]),
+    "wu_nn_ball_scores": (I, [P, I, I, P, I, I, I, P, I, I, P, SZ, P, P, P, P, P, P, P]),
     "wu_fd_ld": (I, [I, I]),
     "wu_fd_workspace_bytes": (SZ, [I, I, I]),
     "wu_fd_cross_gram": (I, [P, I, I, P, I, I, I, P, P]),

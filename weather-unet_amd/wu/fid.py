@@ -368,10 +368,20 @@ def main(argv=None):
                          "K nearest, 1..16; the line gives the median and the smallest nearest distance: leakage and memorisation); a "
                          ".npz path must then hold 'features'")
     ap.add_argument("--nn-threshold", type=float, default=None, metavar="T", help="with --nn: also count the rows closer than T to a row of the first path")
-    ap.add_argument("--nn-report", default=None, metavar="OUT.json", help="with --nn: write wu.retrieval.nearest_report's dict here")
+    ap.add_argument("--nn-report", default=None, metavar="OUT.json",
+                    help="with --nn: write wu.retrieval.nearest_report's dict here; with --nn-radius it gains the full pair list (key 'radius_join')")
+    ap.add_argument("--nn-radius", type=float, default=None, metavar="R",
+                    help="also print, for the rows of the second path, EVERY row of the first within the distance R (wu.retrieval.radius_join: "
+                         "pairs, rows with a hit, the most pairs of one row); a .npz path must then hold 'features'")
+    ap.add_argument("--realism", action="store_true",
+                    help="also print the per-row realism (Kynkaanniemi et al. 2019) and rarity (Han et al. 2022) summary of the rows of the "
+                         "second path against the k-NN manifold of the first (wu.retrieval.ball_scores); a .npz path must then hold 'features'")
+    ap.add_argument("--realism-k", type=int, default=3, help="with --realism: the k of the k-NN radii")
+    ap.add_argument("--realism-report", default=None, metavar="OUT.json", help="with --realism: write wu.retrieval.score_report's dict here")
     args = ap.parse_args(argv)
     stats, banks = _pass_over_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png,
-                                    args.gpu_entropy, fid=True, rows=args.kid or args.prdc or args.fid_rows or args.nn != 0, resize=args.resize)
+                                    args.gpu_entropy, fid=True, rows=args.kid or args.prdc or args.fid_rows or args.nn != 0 or args.nn_radius is not None
+                                    or args.realism, resize=args.resize)
     print(f"FID: {calculate_frechet_distance(*stats[0], *stats[1])}")
     if args.fid_rows:
         from .frechet import frechet_distance
@@ -385,15 +395,28 @@ def main(argv=None):
         from .prdc import precision_recall_density_coverage
         m = precision_recall_density_coverage(*banks, k=args.prdc_k)
         print(f"PRDC: precision {m.precision} recall {m.recall} density {m.density} coverage {m.coverage}")
-    if args.nn:
+    if args.nn or args.nn_radius is not None or args.realism:
         import json
-        from .retrieval import nearest_report, nn_line
+        from . import retrieval
         names = [None if p.endswith(".npz") else [f.name for f in image_files(p)] for p in args.path]
-        rep = nearest_report(banks[1], banks[0], threshold=args.nn_threshold, query_names=names[1], bank_names=names[0], k=args.nn)
-        print(nn_line(rep))
-        if args.nn_report:
+        rep = {}
+        if args.nn:
+            rep = retrieval.nearest_report(banks[1], banks[0], threshold=args.nn_threshold, query_names=names[1], bank_names=names[0], k=args.nn)
+            print(retrieval.nn_line(rep))
+        if args.nn_radius is not None:
+            join = retrieval.radius_join(banks[1], banks[0], args.nn_radius * args.nn_radius)
+            rep["radius_join"] = retrieval.radius_report(*join, args.nn_radius, names[1], names[0])
+            print(retrieval.radius_line(rep["radius_join"]))
+        if args.nn_report and rep:
             with open(args.nn_report, "w") as fh:
                 json.dump(rep, fh)
+        if args.realism:
+            scores = retrieval.ball_scores(banks[1], banks[0], k=args.realism_k)
+            srep = retrieval.score_report(scores, k=args.realism_k, query_names=names[1], bank_names=names[0])
+            print(retrieval.realism_line(srep))
+            if args.realism_report:
+                with open(args.realism_report, "w") as fh:
+                    json.dump(srep, fh)
     return 0
 
 
