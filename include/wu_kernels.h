@@ -955,6 +955,35 @@ int wu_swd_project_sort(const float* desc, int m, const float* dirs, int ndirs, 
 int wu_swd_sort_columns(double* keys, int m, int ncols, void* workspace, void* stream);
 int wu_swd_distance(const double* a, const double* b, int m, int ndirs, double* w, void* stream);
 
+/* ---- Colour-transfer baselines (wu/colour.py): histogram matching and sliced optimal transport of pixel colours --------------------------
+ * A "virtual image" g = r B + b is input image b on its way to target r; its state is (3, n) fp64 in [0, 1] units, n = H W.  `first` is the
+ * g of the first state of a call, so that any run of virtual images can be in flight.  All arithmetic in fp64, every operation rounded on
+ * its own (no FMA); no atomics and no sums across threads: the same inputs give the same bits.  tests/_colour_ref.py restates it.
+ * `rotation` is a HOST array of 9 doubles, row a = axis a; it is copied into the kernels' arguments.
+ *   wu_colour_ot_load          x (B, 3, H, W) with ELEMENT strides, dtype WU_F32, WU_BF16 or WU_SSIM_U8 -> state (nimg, 3, n):
+ *                              s = (double(v) * scale + shift) / L; state v reads image (first + v) % B.
+ *   wu_colour_ot_palette_keys  palette (npal, P, 3) fp64 -> keys (npal * 3, P): key_a = (R[a][0] s_0 + R[a][1] s_1) + R[a][2] s_2, then
+ *                              every row sorted ascending by wu_swd_sort_columns.  workspace: wu_colour_ot_workspace_bytes(1, 1, npal, P).
+ *   wu_colour_ot_step          one iteration on nimg states in place: the keys of every state are projected and sorted (the same sort), and
+ *                              per pixel and axis a, among the n keys of its image, lo = #{key' < key}, hi = #{key' <= key},
+ *                              t = ((lo + hi) P) / (2 n) in int64, delta_a = q[t] - key_a with q the sorted keys of axis a of palette
+ *                              classes[v] (a DEVICE array of nimg ints in 0..npal-1; the caller checks them, an image with a class outside
+ *                              is left unchanged); then d_c = (delta_0 R[0][c] + delta_1 R[1][c]) + delta_2 R[2][c] and
+ *                              s_c = s_c + step * d_c.  workspace: wu_colour_ot_workspace_bytes(nimg, n, npal, P).
+ *   wu_colour_ot_store         u = min(max(s, 0), 1), v = lo + u * span, rint(v) (half to even) when round_int or for WU_SSIM_U8, then
+ *                              fp64 -> fp32 (-> bf16), nearest-even, into y (R, B, 3, H, W) with ELEMENT strides: state v goes to
+ *                              r = (first + v) / B, b = (first + v) % B.
+ * 1 <= n, P <= 2^21.  wu_colour_ot_workspace_bytes returns 0 for anything out of range.  Stream-ordered, caller-owned buffers, no
+ * allocation, no synchronisation. */
+size_t wu_colour_ot_workspace_bytes(int nimg, int n, int npal, int P);
+int wu_colour_ot_load(const void* x, long long xs_n, long long xs_c, long long xs_h, long long xs_w, int dtype, int B, int H, int W,
+                      double scale, double shift, double L, long long first, int nimg, double* state, void* stream);
+int wu_colour_ot_palette_keys(const double* palette, int npal, int P, const double* rotation, double* keys, void* workspace, void* stream);
+int wu_colour_ot_step(double* state, int nimg, int n, const double* palette_keys, int npal, int P, const int* classes,
+                      const double* rotation, double step, void* workspace, void* stream);
+int wu_colour_ot_store(const double* state, long long first, int nimg, void* y, long long ys_r, long long ys_n, long long ys_c,
+                       long long ys_h, long long ys_w, int dtype, int B, int H, int W, double lo, double span, int round_int, void* stream);
+
 /* layout helpers for the module boundary: NHWC `dtype` <-> NCHW fp32 (feature maps returned by
  * SNDisc.forward, disc.py:38; gradients flowing back into them). */
 int wu_nhwc_to_nchw_f32(const void* x, int ldx, float* y_nchw, int N, int H, int W, int C, int dtype, void* stream);
