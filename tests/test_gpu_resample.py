@@ -157,21 +157,21 @@ def test_swd_reader_with_a_filter(tmp_path):
     """python -m wu.swd --size S --filter F reads through the resampler in 8-bit mode: with bilinear it equals the present --size path (the
     training pipeline's Pillow-exact bilinear resize) bit for bit; bicubic is Pillow's bicubic; without --size it is an error."""
     from PIL import Image
-    from wu import swd
+    from wu.files import read_images
     shapes = ((40, 56), (33, 20), (16, 16))
     images = [C.picture(h, w, "mixed", 90 + i) for i, (h, w) in enumerate(shapes)]
     files = []
     for i, a in enumerate(images):
         files.append(str(tmp_path / f"{i}.png"))
         Image.fromarray(a, "RGB").save(files[-1])
-    (plain, r0), = list(swd._read_dir(files, 16, False, DEV))
-    (bil, r1), = list(swd._read_dir(files, 16, False, DEV, filter="bilinear"))
+    (plain, r0), = list(read_images(files, 16, False, DEV))
+    (bil, r1), = list(read_images(files, 16, False, DEV, filter="bilinear"))
     assert r0 == r1 == (-1, 1) and torch.equal(plain, bil)
-    (cub, _), = list(swd._read_dir(files, 16, False, DEV, filter="bicubic"))
+    (cub, _), = list(read_images(files, 16, False, DEV, filter="bicubic"))
     want = np.stack([C.pillow(a, (16, 16), "bicubic", "u8") for a in images]).transpose(0, 3, 1, 2)
     assert np.array_equal(C.bits(cub.cpu().numpy()), C.bits(R.normalised(want)))
     with pytest.raises(ValueError, match="--size"):
-        list(swd._read_dir(files, None, False, DEV, filter="bicubic"))
+        list(read_images(files, None, False, DEV, filter="bicubic"))
 
 
 def test_directory_of_mixed_sizes(tmp_path):

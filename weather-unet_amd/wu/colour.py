@@ -150,15 +150,14 @@ class ClassPalettes:
         them and resized to size x size by the loader's rule (without ``size`` all files of a class must have one size).  The files go
         through in sorted order and the pixels are ``draw_points(seed, N, H, W, P)`` of the whole class, so the palette does not depend on
         ``batch_size``."""
-        from .fid import image_files
-        from .swd import _read_dir
+        from .files import image_files, read_images
         pals = []
         for name, d in dirs.items():
             files = image_files(d)
             if not files:
                 raise RuntimeError(f"no .jpg / .png images in {d}")
             pal, pts, at = None, None, 0
-            for x, rng in _read_dir(files, size, gpu_decode, device, batch_size):
+            for x, rng in read_images(files, size, gpu_decode, device, batch_size):
                 if pts is None:
                     i, y, xx = draw_points(seed, len(files), x.shape[2], x.shape[3], int(P))
                     pts, hw = (i, y, xx), tuple(x.shape[2:])
@@ -291,9 +290,8 @@ class ColourBaseline:
 def transfer_dir(src_dir, out_dir, palettes, iters=20, size=None, seed=0, ext=".png", batch_size=16, device="cuda:0"):
     """Every .jpg / .png file of ``src_dir`` to every class: ``out_dir/NAME/<stem><ext>`` through ``wu.infer_driver.save_images``.
     Returns the number of images read."""
-    from .fid import image_files
+    from .files import image_files, read_images
     from .infer_driver import save_images
-    from .swd import _read_dir
     files = image_files(src_dir)
     if not files:
         raise RuntimeError(f"no .jpg / .png images in {src_dir}")
@@ -301,7 +299,7 @@ def transfer_dir(src_dir, out_dir, palettes, iters=20, size=None, seed=0, ext=".
         os.makedirs(os.path.join(out_dir, name), exist_ok=True)
     palettes.to(device)
     at = 0
-    for x, rng in _read_dir(files, size, False, device, batch_size):
+    for x, rng in read_images(files, size, False, device, batch_size):
         out = transfer(x, palettes, list(range(palettes.num_classes)), iters, seed, 1.0, rng)
         # the writers take [0, 1] floats and truncate v * 255: a byte b goes in as (b + 0.5) / 255, the middle of its bucket
         out01 = (out.float() + 0.5) / 255 if isinstance(rng, str) else (out.float() - rng[0]) / (rng[1] - rng[0])

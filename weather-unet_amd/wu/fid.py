@@ -35,7 +35,6 @@ legacy); paths under different rules raise.
 """
 import argparse
 import os
-import pathlib
 import sys
 
 import numpy as np
@@ -43,6 +42,7 @@ import torch
 
 from . import _lib
 from .features import FeatureBank, as_rows
+from .files import image_files, pass_decoder, read_batches, same_size
 from .inception import InceptionV3, global_avgpool
 from .layout import precision_code, stream_ptr
 
@@ -169,11 +169,6 @@ def inception_score(logits_or_probs, splits=1, is_logits=None):
 # ----------------------------------------------------------------------------------------------
 # command line (fid_score.py)
 # ----------------------------------------------------------------------------------------------
-def image_files(path):
-    p = pathlib.Path(path)
-    return sorted(list(p.glob("*.jpg")) + list(p.glob("*.png")))
-
-
 def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False, features=None, resize=None):
     """(mu, sigma) of a .npz file or of the images in a directory (uint8 batches straight to the GPU).  gpu_decode: read the files
     through wu.jpeg.GPUJpegDecoder instead of the per-file Pillow loop; gpu_decode_png: through wu.png.GPUPngDecoder, which inflates the
@@ -182,9 +177,8 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png
     features: a wu.features.FeatureBank that also receives every feature row (the KID's input); a .npz must then hold ``features``, and its
     ``mu`` / ``sigma`` are taken from the file when it has them and computed from the rows when it does not.
     resize: the model's rule (``InceptionV3(resize=...)``; None: whatever the model has).  ``"clean"`` reads a directory of MIXED sizes on
-    all three read paths, as padded ragged batches through wu.resample; ``"legacy"`` raises on one, as it always has.  A .npz recorded
-    under another rule than ``resize`` raises."""
-    gpu_decode = gpu_decode or gpu_entropy
+    all three read paths, as the padded ragged batches of wu.files; ``"legacy"`` raises on a batch of mixed sizes, as it always has.
+    A .npz recorded under another rule than ``resize`` raises."""
     if path.endswith(".npz"):
         if resize is not None and npz_resize_rule(path) != resize:
             raise ValueError(f"resize rules differ: {path} was recorded under {npz_resize_rule(path)!r}, not {resize!r}")
@@ -195,48 +189,19 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png
     rule = getattr(model, "resize", LEGACY)
     if resize is not None and resize != rule:
         raise ValueError(f"statistics_of_path: resize={resize!r}, but the model was built with resize={rule!r}")
-    from PIL import Image
     files = image_files(path)
     if not files:
         raise RuntimeError(f"no .jpg / .png images in {path}")
     stats = FIDStatistics(model)
     if features is not None and rule != LEGACY:
         features.resize = rule
-    if rule == CLEAN:
-        from .resample import read_batches
-        dec = None
-        if gpu_decode_png:
-            from . import png
-            dec = png.GPUPngDecoder()
-        elif gpu_decode:
-            from .jpeg import GPUJpegDecoder
-            dec = GPUJpegDecoder(entropy="device" if gpu_entropy else "host")
-        try:
-            for batch, sizes in read_batches(files, batch_size, dec):
+    with pass_decoder(gpu_decode, gpu_decode_png, gpu_entropy) as dec:
+        for batch, sizes in read_batches(files, batch_size, dec):
+            if rule == CLEAN:
                 stats.update(batch, features=features, sizes=sizes)
-        finally:
-            if dec is not None:
-                dec.close()
-        return stats.finalize()
-    if gpu_decode or gpu_decode_png:
-        if gpu_decode_png:
-            from . import png
-            dec = png.GPUPngDecoder()
-        else:
-            from .jpeg import GPUJpegDecoder
-            dec = GPUJpegDecoder(entropy="device" if gpu_entropy else "host")
-        try:
-            for i in range(0, len(files), batch_size):
-                batch, sizes = dec.decode_batch(files[i:i + batch_size])
-                if any(s != sizes[0] for s in sizes):
-                    raise ValueError(f"images of different sizes in {path}: {sorted(set(sizes))}")       # np.stack's refusal below
+            else:
+                same_size(sizes, f"in {path}: ")          # per batch, as pytorch-fid's np.stack refuses
                 stats.update(batch, features=features)
-        finally:
-            dec.close()
-        return stats.finalize()
-    for i in range(0, len(files), batch_size):
-        batch = np.stack([np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8) for f in files[i:i + batch_size]])
-        stats.update(torch.from_numpy(batch).cuda(), features=features)
     return stats.finalize()
 
 
@@ -253,7 +218,8 @@ def _npz_statistics_and_features(path, features):
     return stats.finalize()
 
 
-def _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode, gpu_decode_png, gpu_entropy, fid, rows, resize=LEGACY):
+def _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False, *, fid, rows,
+                     resize=LEGACY):
     """What every entry point below shares: the path check, the model loaded once (not at all for .npz files alone) and ONE pass over each
     path.  Returns (stats, banks), a list per path each: (mu, sigma) when ``fid`` and a FeatureBank of the feature rows when ``rows``, None
     otherwise.  Without ``rows`` a .npz is read for ``mu`` / ``sigma`` only; with ``rows`` it must hold ``features``, and without ``fid``

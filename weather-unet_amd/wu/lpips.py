@@ -362,31 +362,15 @@ class LPIPS(nn.Module):
 # command line
 # ----------------------------------------------------------------------------------------------
 def distance_of_dirs(model, dir_a, dir_b, batch_size=32, device="cuda:0"):
-    """The mean LPIPS and the per-layer means over the files of two directories paired by stem (``wu.paired.pair_files``; Pillow, uint8
-    RGB; pairs batched by size): {"lpips", "layers", "pairs"}."""
-    import numpy as np
-    from PIL import Image
-    from .paired import pair_files
-    groups = {}
-    for pa, pb in pair_files(dir_a, dir_b):
-        with Image.open(pa) as ia, Image.open(pb) as ib:
-            if ia.size != ib.size:
-                raise ValueError(f"{pa} is {ia.size[0]} x {ia.size[1]} but {pb} is {ib.size[0]} x {ib.size[1]}")
-            groups.setdefault(ia.size, []).append((pa, pb))
-
-    def batch(paths):
-        a = np.stack([np.asarray(Image.open(p).convert("RGB"), dtype=np.uint8) for p in paths])
-        return torch.from_numpy(a).to(device).permute(0, 3, 1, 2)           # NHWC storage, read through its strides
-
+    """The mean LPIPS and the per-layer means over the files of two directories paired by stem (``wu.files.paired_batches``; Pillow,
+    uint8 RGB; pairs batched by size): {"lpips", "layers", "pairs"}."""
+    from .files import paired_batches
     sums, count = None, 0
-    for size in sorted(groups):
-        ps = groups[size]
-        for i in range(0, len(ps), batch_size):
-            d, per = model.distance(batch([p[0] for p in ps[i:i + batch_size]]), batch([p[1] for p in ps[i:i + batch_size]]), "uint8",
-                                    layers=True, max_images=batch_size)
-            part = torch.cat([d.sum(0, keepdim=True), per.sum(0)])
-            sums = part if sums is None else sums + part
-            count += d.shape[0]
+    for xa, xb in paired_batches(dir_a, dir_b, batch_size, device):
+        d, per = model.distance(xa, xb, "uint8", layers=True, max_images=batch_size)
+        part = torch.cat([d.sum(0, keepdim=True), per.sum(0)])
+        sums = part if sums is None else sums + part
+        count += d.shape[0]
     vals = (sums / count).tolist()
     return {"lpips": vals[0], "layers": vals[1:], "pairs": count}
 

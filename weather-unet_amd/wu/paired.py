@@ -30,12 +30,12 @@ no CPU fallback."""
 import collections
 import ctypes
 import math
-import os
 
 import numpy as np
 import torch
 
 from . import _lib
+from .files import pair_files, paired_batches  # noqa: F401  (pair_files: the name callers know it by here)
 from .layout import stream_ptr
 
 U8 = 2                                  # WU_SSIM_U8, next to _lib.F32 / _lib.BF16
@@ -177,58 +177,16 @@ def paired_metrics(x, y, value_range=(-1, 1), win_size=11, sigma=1.5, K=(0.01, 0
 # ----------------------------------------------------------------------------------------------
 # command line
 # ----------------------------------------------------------------------------------------------
-_EXTENSIONS = (".jpg", ".jpeg", ".png")
-
-
-def _by_stem(d):
-    out = {}
-    for name in sorted(os.listdir(d)):
-        stem, ext = os.path.splitext(name)
-        if ext.lower() in _EXTENSIONS:
-            if stem in out:
-                raise ValueError(f"pair_files: {d} holds two images with the stem {stem!r}")
-            out[stem] = os.path.join(d, name)
-    return out
-
-
-def pair_files(dir_a, dir_b):
-    """[(path_a, path_b)] of the .jpg / .jpeg / .png files of two directories paired by file stem, sorted; ValueError listing the files
-    without a partner."""
-    a, b = _by_stem(dir_a), _by_stem(dir_b)
-    only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
-    if only_a or only_b:
-        raise ValueError(f"pair_files: unpaired files -- only in {dir_a}: {[os.path.basename(a[s]) for s in only_a]}; "
-                         f"only in {dir_b}: {[os.path.basename(b[s]) for s in only_b]}")
-    if not a:
-        raise ValueError(f"pair_files: no .jpg / .jpeg / .png files in {dir_a}")
-    return [(a[s], b[s]) for s in sorted(a)]
-
-
 def metrics_of_dirs(dir_a, dir_b, ms=True, win_size=11, batch_size=32, device="cuda:0"):
     """The means over the paired files of two directories of the per-pair SSIM, MS-SSIM (None with ms=False), PSNR and MAE (in grey levels):
     {"ssim", "ms_ssim", "psnr", "mae", "pairs"}.  Files are read with Pillow as uint8 RGB; a pair of unequal size is an error; pairs are
-    batched by size."""
-    from PIL import Image
-    groups = {}
-    for pa, pb in pair_files(dir_a, dir_b):
-        with Image.open(pa) as ia, Image.open(pb) as ib:
-            if ia.size != ib.size:
-                raise ValueError(f"{pa} is {ia.size[0]} x {ia.size[1]} but {pb} is {ib.size[0]} x {ib.size[1]}")
-            groups.setdefault(ia.size, []).append((pa, pb))
-
-    def batch(paths):
-        a = np.stack([np.asarray(Image.open(p).convert("RGB"), dtype=np.uint8) for p in paths])
-        return torch.from_numpy(a).to(device).permute(0, 3, 1, 2)           # NHWC storage, read through its strides
-
+    batched by size (``wu.files.paired_batches``)."""
     sums, count = None, 0
-    for size in sorted(groups):
-        pairs = groups[size]
-        for i in range(0, len(pairs), batch_size):
-            m = paired_metrics(batch([p[0] for p in pairs[i:i + batch_size]]), batch([p[1] for p in pairs[i:i + batch_size]]), "uint8",
-                               win_size, ms=ms)
-            part = torch.stack([v.sum() for v in m if v is not None])
-            sums = part if sums is None else sums + part
-            count += min(batch_size, len(pairs) - i)
+    for xa, xb in paired_batches(dir_a, dir_b, batch_size, device):
+        m = paired_metrics(xa, xb, "uint8", win_size, ms=ms)
+        part = torch.stack([v.sum() for v in m if v is not None])
+        sums = part if sums is None else sums + part
+        count += xa.shape[0]
     vals = (sums / count).tolist()
     return {"ssim": vals[0], "ms_ssim": vals[1] if ms else None, "psnr": vals[-2], "mae": vals[-1], "pairs": count}
 

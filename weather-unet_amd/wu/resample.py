@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .files import padded_batch, read_batches, resize_files  # noqa: F401  (they read files for this module: wu.files)
 from .layout import empty_nhwc, require_cuda, stream_ptr, torch_dtype
 
 FILTERS = ("box", "bilinear", "bicubic", "lanczos")
@@ -237,36 +238,3 @@ class GPUResampler:
         x = empty_nhwc(batch.shape[0], cpad, ho, wo, torch_dtype(code), batch.device)
         self._launch(batch, sizes, value_range, _OUT["inception"], x, cpad, cpad, code, normalize)
         return x
-
-
-# ----------------------------------------------------------------------------------------------
-# files -> padded batches -> resampled batches: the one reader of the metric commands
-# ----------------------------------------------------------------------------------------------
-def padded_batch(arrays, device):
-    """(h, w, 3) uint8 arrays of any sizes -> ((N, Hmax, Wmax, 3) uint8 CUDA tensor, zero padded, [(h, w)])."""
-    sizes = [(int(a.shape[0]), int(a.shape[1])) for a in arrays]
-    hm, wm = max(s[0] for s in sizes), max(s[1] for s in sizes)
-    host = np.zeros((len(arrays), hm, wm, 3), dtype=np.uint8)
-    for k, a in enumerate(arrays):
-        host[k, :a.shape[0], :a.shape[1]] = a
-    return torch.from_numpy(host).to(device), sizes
-
-
-def read_batches(files, batch_size, decoder=None, device="cuda"):
-    """Generator of (padded uint8 batch, [(h, w)]) over ``files``: through ``decoder.decode_batch`` (a GPUJpegDecoder / GPUPngDecoder) when
-    one is given, through Pillow otherwise -- the same padded batch either way."""
-    from PIL import Image
-    for i in range(0, len(files), batch_size):
-        part = files[i:i + batch_size]
-        if decoder is not None:
-            batch, sizes = decoder.decode_batch(part)
-            yield batch, [(int(h), int(w)) for h, w in sizes]
-        else:
-            yield padded_batch([np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8) for f in part], device)
-
-
-def resize_files(files, size, filter="bicubic", mode="f32", out="nchw", batch_size=64, decoder=None, device="cuda", band=None):
-    """Generator over ``files``: each batch read (``read_batches``) and resized to ``size`` by one GPUResampler."""
-    rs = GPUResampler(size, filter, mode, out, band)
-    for batch, sizes in read_batches(files, batch_size, decoder, device):
-        yield rs(batch, sizes)

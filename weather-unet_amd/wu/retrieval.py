@@ -423,6 +423,7 @@ def figure_rows(dist2, rows):
 
 
 def _read_cell(path, cell):
+    """Not wu.files.read_rgb: the resize is Pillow's, on the Image, before it becomes an array."""
     from PIL import Image
     with Image.open(path) as im:
         im = im.convert("RGB")
@@ -470,6 +471,7 @@ def save_realism_figure(path, query_files, bank_files, scores, rows=16, cell=128
 
 def main(argv=None):
     from . import fid
+    from .files import image_files
     from .inception import InceptionV3
     ap = argparse.ArgumentParser(prog="python -m wu.retrieval", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                  description="Nearest bank images of every query image on InceptionV3 features: the memorisation figure, "
@@ -511,9 +513,9 @@ def main(argv=None):
         ap.error("--groups needs --self")
     if args.realism_worst and not args.figure:
         ap.error("--realism-worst needs --figure")
-    _, banks = fid._pass_over_paths(paths, args.weights, args.batch_size, args.dims, args.precision, False, False, False, fid=False, rows=True)
+    _, banks = fid._pass_over_paths(paths, args.weights, args.batch_size, args.dims, args.precision, fid=False, rows=True)
     q, b = banks[0], banks[-1]
-    files = [None if p.endswith(".npz") else fid.image_files(p) for p in paths]
+    files = [None if p.endswith(".npz") else image_files(p) for p in paths]
     qf, bf = files[0], files[-1]
     dist2, index = topk(q, b, args.k, exclude_self=args.self_)
     rep = report_from_topk(dist2, index, args.threshold, args.self_, None if qf is None else [f.name for f in qf],

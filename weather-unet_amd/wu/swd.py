@@ -264,52 +264,6 @@ def swd(images_a, images_b, P=128, repeats=4, dirs_per_repeat=128, seed=0, value
 # ----------------------------------------------------------------------------------------------
 # command line
 # ----------------------------------------------------------------------------------------------
-def _read_dir(files, size, gpu_decode, device, batch_size=64, filter=None):
-    """The files as uint8 NHWC batches (read through their strides), or as (N, 3, S, S) float32 in [-1, 1] with ``size``.  ``filter``
-    (with ``size``): resize with that Pillow filter in 8-bit mode through wu.resample instead of the training pipeline's bilinear one."""
-    from PIL import Image
-    dec = pipe = None
-    if filter is not None and not size:
-        raise ValueError("--filter chooses how --size resizes: give --size")
-    if gpu_decode:
-        from .jpeg import GPUJpegDecoder
-        dec = GPUJpegDecoder()
-    if filter is not None:
-        from .resample import resize_files
-        try:
-            for x in resize_files(files, size, filter, "u8", "nchw", batch_size, dec, device):
-                yield x, (-1, 1)
-        finally:
-            if dec is not None:
-                dec.close()
-        return
-    if size:
-        from .input_pipeline import GPUInputPipeline
-        pipe = GPUInputPipeline(size, train=False)
-    try:
-        for i in range(0, len(files), batch_size):
-            part = files[i:i + batch_size]
-            if dec is not None:
-                batch, sizes = dec.decode_batch(part)
-            else:
-                arrays = [np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8) for f in part]
-                sizes = [a.shape[:2] for a in arrays]
-                hm, wm = max(s[0] for s in sizes), max(s[1] for s in sizes)
-                host = np.zeros((len(arrays), hm, wm, 3), dtype=np.uint8)
-                for k, a in enumerate(arrays):
-                    host[k, :a.shape[0], :a.shape[1]] = a
-                batch = torch.from_numpy(host).to(device)
-            if pipe is not None:
-                yield pipe(batch.contiguous(), [tuple(int(v) for v in s) for s in sizes]), (-1, 1)
-            else:
-                if any(tuple(s) != tuple(sizes[0]) for s in sizes):
-                    raise ValueError(f"images of different sizes ({sorted(set(tuple(int(v) for v in s) for s in sizes))}): give --size")
-                yield batch.permute(0, 3, 1, 2), "uint8"
-    finally:
-        if dec is not None:
-            dec.close()
-
-
 def swd_of_dirs(dir_a, dir_b, size=None, P=128, repeats=4, dirs_per_repeat=128, seed=0, gpu_decode=False, device="cuda:0", log=print,
                 filter=None):
     """SWDResult of the .jpg / .png files of two directories, and the number of images used per set.  Images are resized (through
@@ -317,7 +271,7 @@ def swd_of_dirs(dir_a, dir_b, size=None, P=128, repeats=4, dirs_per_repeat=128, 
     larger one, drawn from ``seed``, and a line through ``log`` that says so.  ``filter`` (box, bilinear, bicubic, lanczos; with ``size``):
     resize with that Pillow filter in 8-bit mode through ``wu.resample`` instead."""
     from .evaluate import SlicedWasserstein
-    from .fid import image_files
+    from .files import image_files, read_images
     fa, fb = image_files(dir_a), image_files(dir_b)
     if not fa or not fb:
         raise RuntimeError(f"no .jpg / .png images in {dir_a if not fa else dir_b}")
@@ -332,8 +286,8 @@ def swd_of_dirs(dir_a, dir_b, size=None, P=128, repeats=4, dirs_per_repeat=128, 
         else:
             fb = [fb[i] for i in keep]
     acc = SlicedWasserstein(P=P, repeats=repeats, dirs_per_repeat=dirs_per_repeat, seed=seed)
-    for (xa, ra), (xb, rb) in zip(_read_dir(fa, size, gpu_decode, device, filter=filter),
-                                      _read_dir(fb, size, gpu_decode, device, filter=filter)):
+    for (xa, ra), (xb, rb) in zip(read_images(fa, size, gpu_decode, device, filter=filter),
+                                      read_images(fb, size, gpu_decode, device, filter=filter)):
         acc.value_range = ra
         acc.update(xa, xb)
     return acc.compute(), n
