@@ -444,7 +444,8 @@ int wu_image_color_jitter(uint8_t* img_u8, const float* factors, const int* orde
  *
  * Decoded natively: 8-bit sequential Huffman (SOF0, SOF1), one interleaved scan, greyscale or YCbCr (JFIF marker, or Adobe marker
  * with transform 1, or neither and component ids 1, 2, 3) with luma sampling 1x1 / 2x1 / 2x2 and chroma 1x1, restart intervals.
- * Everything else is REPORTED (supported = 0 and a reason), never guessed at. */
+ * Everything else is REPORTED (supported = 0 and a reason), never guessed at.  Opt-in through wu_jpeg_parse_ex's flags: progressive
+ * Huffman frames (SOF2; the host half runs every scan into the same coefficient buffer) and luma sampling 1x2 (4:4:0). */
 #define WU_JPEG_OK 0
 #define WU_JPEG_NOT_JPEG 1       /* no SOI: another format */
 #define WU_JPEG_CORRUPT 2        /* truncated or inconsistent header */
@@ -457,10 +458,19 @@ int wu_image_color_jitter(uint8_t* img_u8, const float* factors, const int* orde
 #define WU_JPEG_SAMPLING 9       /* 4:4:0, 4:1:1, sub-sampled luma ... */
 #define WU_JPEG_MULTISCAN 10     /* components spread over several scans */
 #define WU_JPEG_MAGNITUDE 11     /* set by the entropy stage: a block exceeds the IDCT's overflow bound */
+#define WU_JPEG_PROGRESSIVE_INCOMPLETE 12   /* set by the entropy stage: the scans do not deliver every coefficient at full precision, or
+                                               follow a script libjpeg only warns about */
 #define WU_JPEG_MODE_GREY 0
 #define WU_JPEG_MODE_444 1
 #define WU_JPEG_MODE_H2V1 2      /* 4:2:2 */
 #define WU_JPEG_MODE_H2V2 3      /* 4:2:0 */
+#define WU_JPEG_MODE_H1V2 4      /* 4:4:0: only with WU_JPEG_ALLOW_H1V2 */
+/* wu_jpeg_parse_ex flags: what is decoded natively BEYOND the list above.  Opt-in; wu_jpeg_parse is flags = 0. */
+#define WU_JPEG_ALLOW_PROGRESSIVE 1   /* SOF2, 8-bit, grey or YCbCr: any legal scan script that ends with every coefficient at Al = 0 */
+#define WU_JPEG_ALLOW_H1V2 2          /* luma sampling 1x2 (a 4:2:2 file after a lossless 90 degree rotation) */
+/* wu_jpeg_info.reserved: the frame kind */
+#define WU_JPEG_FRAME_SEQUENTIAL 0    /* SOF0 / SOF1, one interleaved scan */
+#define WU_JPEG_FRAME_PROGRESSIVE 1   /* SOF2: scan_offset is the first scan's data; td / ta are unused (every scan names its own) */
 typedef struct wu_jpeg_info {
     long long coef_bytes;            /* coefficient storage the image needs: total_blocks * 64 int16 */
     int height, width, ncomp, mode;
@@ -473,18 +483,26 @@ typedef struct wu_jpeg_info {
     int scan_offset;                 /* first byte of the entropy-coded data */
     int dht_off[8], dqt_off[4];      /* byte offsets of the table bodies inside the file (DC 0-3, AC 0-3; 0 = absent) */
     int max_block_l1;                /* written by the entropy stage: max over blocks of sum |c * q| */
-    int reserved;
+    int reserved;                    /* WU_JPEG_FRAME_* */
 } wu_jpeg_info;
 size_t wu_jpeg_info_bytes(void);
 /* Walks the markers up to SOS.  Returns 0 whenever `info` was filled; a file that cannot be decoded natively has
  * info->supported == 0 and info->reason set. */
 int wu_jpeg_parse(const uint8_t* data, size_t nbytes, wu_jpeg_info* info);
+/* The same with an OR of WU_JPEG_ALLOW_* in `flags`: a progressive frame (8-bit, 1 or 3 components under the colour-space rule above,
+ * sampling as supported after the flags) and / or luma sampling 1x2 are reported supported instead of refused. */
+int wu_jpeg_parse_ex(const uint8_t* data, size_t nbytes, wu_jpeg_info* info, int flags);
 /* Huffman-decodes the scan of a file wu_jpeg_parse reported supported into caller-owned memory: `coef` receives
  * info->total_blocks blocks of 64 int16 QUANTISED coefficients in natural (row-major) order, plane of component 0 first, blocks
  * of a plane in raster order; `qtab_out` receives 3 tables of 64 uint16 in natural order (unused ones filled with 1).
- * Returns 0, or 1 when a block's sum |c * q| exceeds the bound under which the 16- / 32-bit IDCT arithmetic cannot overflow
- * (reason WU_JPEG_MAGNITUDE: decode such a file elsewhere), or a negative code with a message for corrupt data (bad Huffman code
- * or table, coefficient index past 63, bad restart sequence, premature marker or end of data, buffer too small). */
+ * A progressive frame: walks the markers from the start of the file to EOI and runs EVERY scan into the (zeroed) buffer; the
+ * quantisation table of a component is the one in force when its first scan starts.
+ * Returns 0, or 1 with info->reason set when the file is to be decoded elsewhere -- WU_JPEG_MAGNITUDE: a block's sum |c * q| exceeds
+ * the bound under which the 16- / 32-bit IDCT arithmetic cannot overflow; WU_JPEG_PROGRESSIVE_INCOMPLETE: the scans of a progressive
+ * file leave a coefficient of a component short of full precision (libjpeg then smooths between blocks) or follow a script libjpeg
+ * warns about; WU_JPEG_QTABLE16: a 16-bit table defined between scans -- or a negative code with a message for corrupt data (bad
+ * Huffman code or table, coefficient index past 63 or past the scan's band, bad restart sequence, premature marker or end of data,
+ * inconsistent scan header, buffer too small). */
 int wu_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, wu_jpeg_info* info, int16_t* coef, size_t coef_capacity_bytes,
                            uint16_t* qtab_out);
 int wu_jpeg_max_block_l1(void);

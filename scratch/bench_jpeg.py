@@ -2,6 +2,8 @@
 
     python scratch/bench_jpeg.py                      # host comparison + host breakdown + device timing (events) + end-to-end line
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o jpeg -- python scratch/bench_jpeg.py --mode device      # kernel times of ONE batch, run of its own
+    python scratch/bench_jpeg.py --mode progressive   # the same pixels saved with progressive=True: Pillow, the default decoder (every
+                                                      # file takes its Pillow fallback) and coverage="extended" (native), alternating
 
 Workload: 512 generated photo-like JPEGs, 500x375 and 375x500 mixed, quality 85, 4:2:0, held in memory as bytes (no disk in the
 timing); batches of 64; 16 host threads on both sides; warm-up, then >= 20 batches per run, 5 runs, the two paths alternating inside
@@ -36,13 +38,13 @@ def photo_like(h, w, seed):
     return np.clip(img + rng.normal(0, 6, (h, w, 3)), 0, 255).astype(np.uint8)
 
 
-def make_files(n):
+def make_files(n, progressive=False):
     from PIL import Image
     out = []
     for k in range(n):
         h, w = (375, 500) if k % 2 == 0 else (500, 375)
         f = io.BytesIO()
-        Image.fromarray(photo_like(h, w, k)).save(f, "JPEG", quality=85, subsampling=2)
+        Image.fromarray(photo_like(h, w, k)).save(f, "JPEG", quality=85, subsampling=2, **(dict(progressive=True) if progressive else {}))
         out.append(f.getvalue())
     return out
 
@@ -71,7 +73,7 @@ def algorithm_bytes(infos, hmax, wmax):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", default="all", choices=["all", "host", "device", "e2e"])
+    ap.add_argument("--mode", default="all", choices=["all", "host", "device", "e2e", "progressive"])
     ap.add_argument("--files", type=int, default=512)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--threads", type=int, default=16)
@@ -86,7 +88,7 @@ def main():
     threads = min(16, a.threads)
     res = {"cmd": " ".join(sys.argv), "pillow_version": PIL.__version__, "libjpeg": features.version("jpg"), "libjpeg_turbo": bool(features.check_feature("libjpeg_turbo")),
            "cpu": cpu_model(), "threads": threads, "files": a.files, "batch": a.batch, "gpu": torch.cuda.get_device_name(0)}
-    files = make_files(a.files)
+    files = make_files(a.files, progressive=a.mode == "progressive")
     res["mean_file_bytes"] = sum(map(len, files)) / len(files)
     batches = [files[i:i + a.batch] for i in range(0, len(files), a.batch)]
     dev = torch.device("cuda:0")
@@ -113,7 +115,51 @@ def main():
 
     # the two paths produce the same tensor (checked once, outside the timing)
     assert torch.equal(pillow_batch(batches[0]), native_batch(batches[0]))
-    assert dec.stats["fallback"] == 0
+    assert dec.stats["fallback"] == (len(batches[0]) if a.mode == "progressive" else 0)
+
+    if a.mode == "progressive":
+        # The progressive copy of the set.  "fallback": the default decoder, where every file is refused ("progressive") and decoded by
+        # Pillow on the worker thread -- what a revision without the extended coverage does with these files; "extended": the scans run
+        # natively on the worker threads.  A library without wu_jpeg_parse_ex measures the first two only.
+        paths = [("pillow", pillow_batch), ("fallback", native_batch)]
+        ext = None
+        if hasattr(jpeg, "COVERAGE"):
+            ext = GPUJpegDecoder(dev, threads=threads, coverage="extended")
+
+            def extended_batch(items):
+                t, _ = ext.decode_batch(items)
+                torch.cuda.synchronize()
+                return t
+            assert torch.equal(pillow_batch(batches[0]), extended_batch(batches[0])) and ext.stats["fallback"] == 0
+            paths.append(("extended", extended_batch))
+        for _, fn in paths:
+            for b in batches[:3]:
+                fn(b)
+        runs = {name: [] for name, _ in paths}
+        for r in range(a.runs):
+            for name, fn in paths[r % len(paths):] + paths[:r % len(paths)]:
+                w0, c0 = time.perf_counter(), time.process_time()
+                n = 0
+                for _ in range(a.passes):
+                    for b in batches:
+                        fn(b)
+                        n += len(b)
+                runs[name].append({"images_per_s": n / (time.perf_counter() - w0), "cpu_s_per_image": (time.process_time() - c0) / n})
+        res["progressive"] = {name: {k: spread([x[k] for x in runs[name]]) for k in ("images_per_s", "cpu_s_per_image")} for name in runs}
+        res["progressive"]["batches_per_run"] = a.passes * len(batches)
+        if ext is not None:                                              # one thread: the scans of one file against Pillow's decode of it
+            lib = jpeg._lib.load()
+            coef = np.empty(8 << 20, dtype=np.int16)
+            q = np.empty((3, 64), dtype=np.uint16)
+            t0 = time.perf_counter()
+            for b in files[:128]:
+                info = jpeg._parse_bytes(lib, b, jpeg.COVERAGE["extended"])
+                jpeg._entropy_into(lib, b, info, coef.ctypes.data, coef.nbytes, q.ctypes.data)
+            t1 = time.perf_counter()
+            for b in files[:128]:
+                pillow_one(b)
+            res["progressive"]["single_thread_s_per_image"] = {"parse_and_all_scans": (t1 - t0) / 128, "pillow_decode": (time.perf_counter() - t1) / 128}
+            ext.close()
 
     if a.mode in ("all", "host"):
         for fn in (pillow_batch, native_batch):                         # warm-up: thread pools, pinned staging, allocator

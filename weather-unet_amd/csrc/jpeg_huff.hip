@@ -58,6 +58,8 @@ bool info_ok(const wu_jpeg_info* info) {
     if (!info || info->supported != 1 || info->ncomp < 1 || info->ncomp > 3 || info->mcus_x <= 0 || info->mcus_y <= 0 || info->mcus_x > 8192 ||
         info->mcus_y > 8192 || info->restart_interval < 0)
         return false;
+    // the device walk knows one interleaved baseline scan with luma 1x1 / 2x1 / 2x2: what wu_jpeg_parse_ex's flags add is not staged
+    if (info->reserved != WU_JPEG_FRAME_SEQUENTIAL || info->mode == WU_JPEG_MODE_H1V2) return false;
     long long blocks = 0;
     for (int c = 0; c < info->ncomp; ++c) {
         if (info->hs[c] < 1 || info->hs[c] > 2 || info->vs[c] < 1 || info->vs[c] > 2 || (c > 0 && (info->hs[c] != 1 || info->vs[c] != 1)) ||

@@ -108,6 +108,7 @@ SIGNATURES = {
     "wu_image_color_jitter": (I, [P, P, P, P, I, I, P]),
     "wu_jpeg_info_bytes": (SZ, []),
     "wu_jpeg_parse": (I, [P, SZ, P]),
+    "wu_jpeg_parse_ex": (I, [P, SZ, P, I]),
     "wu_jpeg_entropy_decode": (I, [P, SZ, P, P, SZ, P]),
     "wu_jpeg_max_block_l1": (I, []),
     "wu_jpeg_desc_bytes": (SZ, []),

@@ -35,7 +35,7 @@ class JpegBatchLoader:
     advances the seed.  Leaving an epoch early (break, exception, ``close()``) stops and joins its background thread."""
 
     def __init__(self, paths, targets=None, batch_size=16, pipeline=None, decoder=None, shuffle=False, sample_weights=None,
-                 num_samples=None, seed=None, drop_last=False, prefetch=2, png_decode=False):
+                 num_samples=None, seed=None, drop_last=False, prefetch=2, png_decode=False, jpeg_coverage="baseline"):
         self.paths = list(paths)
         if not self.paths:
             raise ValueError("JpegBatchLoader: no files")
@@ -55,7 +55,7 @@ class JpegBatchLoader:
             decoder = GPUPngDecoder()
         if decoder is None:
             from .jpeg import GPUJpegDecoder
-            decoder = GPUJpegDecoder()
+            decoder = GPUJpegDecoder(coverage=jpeg_coverage)          # "extended": progressive and 4:4:0 files natively too (opt-in)
         self.decoder = decoder
         self.epoch = 0
         self._active = []

@@ -169,11 +169,13 @@ def inception_score(logits_or_probs, splits=1, is_logits=None):
 # ----------------------------------------------------------------------------------------------
 # command line (fid_score.py)
 # ----------------------------------------------------------------------------------------------
-def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False, features=None, resize=None):
+def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False, features=None, resize=None,
+                       gpu_extended=False):
     """(mu, sigma) of a .npz file or of the images in a directory (uint8 batches straight to the GPU).  gpu_decode: read the files
     through wu.jpeg.GPUJpegDecoder instead of the per-file Pillow loop; gpu_decode_png: through wu.png.GPUPngDecoder, which inflates the
     segmented PNGs wu.png_enc writes on the GPU and hands every other file to Pillow -- the same uint8 batch, hence the same statistics.
-    gpu_entropy (implies gpu_decode): the JPEG decoder also Huffman-decodes on the GPU (``entropy="device"``).  All off by default.
+    gpu_entropy (implies gpu_decode): the JPEG decoder also Huffman-decodes on the GPU (``entropy="device"``).  gpu_extended (implies
+    gpu_decode): the JPEG decoder reads progressive and 4:4:0 files natively too (``coverage="extended"``).  All off by default.
     features: a wu.features.FeatureBank that also receives every feature row (the KID's input); a .npz must then hold ``features``, and its
     ``mu`` / ``sigma`` are taken from the file when it has them and computed from the rows when it does not.
     resize: the model's rule (``InceptionV3(resize=...)``; None: whatever the model has).  ``"clean"`` reads a directory of MIXED sizes on
@@ -195,7 +197,7 @@ def statistics_of_path(path, model, batch_size, gpu_decode=False, gpu_decode_png
     stats = FIDStatistics(model)
     if features is not None and rule != LEGACY:
         features.resize = rule
-    with pass_decoder(gpu_decode, gpu_decode_png, gpu_entropy) as dec:
+    with pass_decoder(gpu_decode, gpu_decode_png, gpu_entropy, gpu_extended) as dec:
         for batch, sizes in read_batches(files, batch_size, dec):
             if rule == CLEAN:
                 stats.update(batch, features=features, sizes=sizes)
@@ -219,7 +221,7 @@ def _npz_statistics_and_features(path, features):
 
 
 def _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode=False, gpu_decode_png=False, gpu_entropy=False, *, fid, rows,
-                     resize=LEGACY):
+                     resize=LEGACY, gpu_extended=False):
     """What every entry point below shares: the path check, the model loaded once (not at all for .npz files alone) and ONE pass over each
     path.  Returns (stats, banks), a list per path each: (mu, sigma) when ``fid`` and a FeatureBank of the feature rows when ``rows``, None
     otherwise.  Without ``rows`` a .npz is read for ``mu`` / ``sigma`` only; with ``rows`` it must hold ``features``, and without ``fid``
@@ -245,7 +247,8 @@ def _pass_over_paths(paths, weights, batch_size, dims, precision, gpu_decode=Fal
             st = None
         else:
             st = statistics_of_path(p, model, batch_size, gpu_decode, gpu_decode_png, gpu_entropy, features=bank,
-                                    resize=None if p.endswith(".npz") else resize)      # a .npz keeps its own rule (checked above)
+                                    resize=None if p.endswith(".npz") else resize,      # a .npz keeps its own rule (checked above)
+                                    gpu_extended=gpu_extended)
         stats.append(st if fid else None)
         banks.append(bank)
     return stats, banks
@@ -307,6 +310,9 @@ def main(argv=None):
     ap.add_argument("--gpu-entropy", action="store_true",
                     help="with --gpu-decode (implied): Huffman-decode the JPEG scans on the GPU too, so that the compressed scan and not the "
                          "coefficients goes over the link")
+    ap.add_argument("--gpu-decode-extended", action="store_true",
+                    help="with --gpu-decode (implied): decode progressive and 4:4:0 JPEG files natively too (coverage='extended'; the scans "
+                         "of a progressive file are run on the host threads) instead of handing them to Pillow; not with --gpu-entropy")
     ap.add_argument("--gpu-decode-png", action="store_true",
                     help="decode segmented PNG files (what wu.png_enc writes) with wu.png.GPUPngDecoder (HIP kernels); other files go to Pillow")
     ap.add_argument("--resize", default=LEGACY, choices=[LEGACY, CLEAN],
@@ -347,7 +353,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     stats, banks = _pass_over_paths(args.path, args.weights, args.batch_size, args.dims, args.precision, args.gpu_decode, args.gpu_decode_png,
                                     args.gpu_entropy, fid=True, rows=args.kid or args.prdc or args.fid_rows or args.nn != 0 or args.nn_radius is not None
-                                    or args.realism, resize=args.resize)
+                                    or args.realism, resize=args.resize, gpu_extended=args.gpu_decode_extended)
     print(f"FID: {calculate_frechet_distance(*stats[0], *stats[1])}")
     if args.fid_rows:
         from .frechet import frechet_distance

@@ -80,16 +80,18 @@ def padded_batch(arrays, device):
 
 
 @contextlib.contextmanager
-def pass_decoder(gpu_decode=False, gpu_decode_png=False, gpu_entropy=False):
+def pass_decoder(gpu_decode=False, gpu_decode_png=False, gpu_entropy=False, gpu_extended=False):
     """The decoder of one pass over a directory, closed on every way out: a wu.png.GPUPngDecoder with ``gpu_decode_png``, else a
-    wu.jpeg.GPUJpegDecoder with ``gpu_decode`` or ``gpu_entropy`` (which implies it and selects ``entropy="device"``), else None: Pillow."""
+    wu.jpeg.GPUJpegDecoder with ``gpu_decode`` or ``gpu_entropy`` (which implies it and selects ``entropy="device"``) or ``gpu_extended``
+    (which implies it too and selects ``coverage="extended"``: progressive and 4:4:0 files natively; not with ``gpu_entropy``), else
+    None: Pillow."""
     dec = None
     if gpu_decode_png:
         from .png import GPUPngDecoder
         dec = GPUPngDecoder()
-    elif gpu_decode or gpu_entropy:
+    elif gpu_decode or gpu_entropy or gpu_extended:
         from .jpeg import GPUJpegDecoder
-        dec = GPUJpegDecoder(entropy="device" if gpu_entropy else "host")
+        dec = GPUJpegDecoder(entropy="device" if gpu_entropy else "host", coverage="extended" if gpu_extended else "baseline")
     try:
         yield dec
     finally:
@@ -117,14 +119,15 @@ def resize_files(files, size, filter="bicubic", mode="f32", out="nchw", batch_si
         yield rs(batch, sizes)
 
 
-def read_images(files, size=None, gpu_decode=False, device="cuda:0", batch_size=64, filter=None):
+def read_images(files, size=None, gpu_decode=False, device="cuda:0", batch_size=64, filter=None, gpu_extended=False):
     """Generator of (x, value_range) over ``files``, every x of one image size.  Without ``size``: the uint8 NHWC batch as an NCHW view
     (read through its strides) with the range ``"uint8"``; a batch of mixed sizes raises.  With ``size``: (N, 3, S, S) float32 in
     ``(-1, 1)`` from wu.input_pipeline (its bilinear resize), or with ``filter`` too from wu.resample with that Pillow filter in 8-bit
-    mode.  ``gpu_decode``: read through wu.jpeg.GPUJpegDecoder, closed when the generator ends or is abandoned."""
+    mode.  ``gpu_decode``: read through wu.jpeg.GPUJpegDecoder, closed when the generator ends or is abandoned; ``gpu_extended``: the
+    same with ``coverage="extended"``."""
     if filter is not None and not size:
         raise ValueError("--filter chooses how --size resizes: give --size")
-    with pass_decoder(gpu_decode) as dec:
+    with pass_decoder(gpu_decode, gpu_extended=gpu_extended) as dec:
         if filter is not None:
             for x in resize_files(files, size, filter, "u8", "nchw", batch_size, dec, device):
                 yield x, (-1, 1)

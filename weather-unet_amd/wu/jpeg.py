@@ -15,6 +15,9 @@ same worker thread, counted in ``stats`` and copied into its slot: the batch is 
 entropy-coded bytes of every file into the staging buffer (``scan_stage``), the compressed scan goes over the link instead of two bytes
 per sample of coefficients, and ``finish`` waits once per batch for the device's verdict on every image.  Opt-in; the default is "host".
 
+``GPUJpegDecoder(coverage="extended")`` decodes progressive files (every scan run on the host threads, csrc/jpeg_host.h) and 4:4:0
+sampling natively instead of handing them to Pillow.  Opt-in; with the default "baseline" they are refused and counted as before.
+
 ``parse``, ``entropy_decode`` and ``scan_stage`` are host-only and work without a GPU.
 """
 import ctypes
@@ -28,9 +31,12 @@ from . import _codec, _lib
 from ._codec import MAX_THREADS  # noqa: F401 -- a public name of this module
 from .layout import stream_ptr
 
-MODE_GREY, MODE_444, MODE_H2V1, MODE_H2V2 = 0, 1, 2, 3
+MODE_GREY, MODE_444, MODE_H2V1, MODE_H2V2, MODE_H1V2 = 0, 1, 2, 3, 4
 REASONS = {0: "ok", 1: "not-jpeg", 2: "corrupt-header", 3: "progressive", 4: "arithmetic", 5: "precision", 6: "lossless",
-           7: "colorspace", 8: "qtable16", 9: "sampling", 10: "multiscan", 11: "magnitude"}
+           7: "colorspace", 8: "qtable16", 9: "sampling", 10: "multiscan", 11: "magnitude", 12: "progressive-incomplete"}
+ALLOW_PROGRESSIVE, ALLOW_H1V2 = 1, 2          # WU_JPEG_ALLOW_*: the flags of wu_jpeg_parse_ex
+COVERAGE = {"baseline": 0, "extended": ALLOW_PROGRESSIVE | ALLOW_H1V2}
+FRAME_SEQUENTIAL, FRAME_PROGRESSIVE = 0, 1    # WU_JPEG_FRAME_*: JpegInfo.reserved
 HUFF_STATUS = {0: "ok", 11: "magnitude"}          # a device status word by name; every other value: "corrupt-scan"
 DHT_BYTES = 6 * 272       # raw DHT records of one image (csrc/jpeg_huff.hip kDhtImage)
 DEFAULT_SUBSEQ_BITS = 1024          # WU_JPEG_HUFF_DEFAULT_SUBSEQ_BITS: the lowest kernel time of 256 / 512 / 1024 / 2048 (profiles/jpeg_huff_bench.md)
@@ -50,6 +56,10 @@ class JpegInfo(ctypes.Structure):
     @property
     def reason_name(self):
         return REASONS.get(self.reason, str(self.reason))
+
+    @property
+    def progressive(self):
+        return self.reserved == FRAME_PROGRESSIVE
 
     @property
     def sampling(self):
@@ -77,22 +87,33 @@ class JpegError(ValueError):
     """Corrupt entropy-coded data (bad Huffman code, bad restart sequence, premature end ...)."""
 
 
-def _parse_bytes(lib, data):
+def _coverage_flags(coverage, who):
+    if coverage not in COVERAGE:
+        raise ValueError(f"{who}: coverage must be 'baseline' or 'extended', got {coverage!r}")
+    return COVERAGE[coverage]
+
+
+def _parse_bytes(lib, data, flags=0):
     info = JpegInfo()
-    _lib.check(lib.wu_jpeg_parse(data, len(data), ctypes.byref(info)), "wu_jpeg_parse")
+    if flags:
+        _lib.check(lib.wu_jpeg_parse_ex(data, len(data), ctypes.byref(info), flags), "wu_jpeg_parse_ex")
+    else:
+        _lib.check(lib.wu_jpeg_parse(data, len(data), ctypes.byref(info)), "wu_jpeg_parse")
     return info
 
 
-def parse(data):
+def parse(data, coverage="baseline"):
     """Header of a JPEG (bytes or path): a JpegInfo with height, width, sampling, restart_interval, supported, reason_name ...
-    Host only."""
+    ``coverage="extended"``: progressive frames and 4:4:0 sampling are reported supported too.  Host only."""
+    flags = _coverage_flags(coverage, "wu.jpeg.parse")
     lib = _lib.load()
     assert lib.wu_jpeg_info_bytes() == ctypes.sizeof(JpegInfo)
-    return _parse_bytes(lib, _codec.read(data))
+    return _parse_bytes(lib, _codec.read(data), flags)
 
 
 def _entropy_into(lib, data, info, coef_ptr, capacity, qtab_ptr):
-    """0 = decoded, 1 = over the magnitude bound; raises JpegError on corrupt data."""
+    """0 = decoded, 1 = refused with ``info.reason`` set (over the magnitude bound; an incomplete progressive file); raises JpegError
+    on corrupt data."""
     rc = lib.wu_jpeg_entropy_decode(data, len(data), ctypes.byref(info), coef_ptr, capacity, qtab_ptr)
     if rc < 0:
         msg = lib.wu_last_error()
@@ -100,18 +121,20 @@ def _entropy_into(lib, data, info, coef_ptr, capacity, qtab_ptr):
     return rc
 
 
-def entropy_decode(data):
+def entropy_decode(data, coverage="baseline"):
     """Host stage alone (tests, tools): returns (planes, qtabs, info) with planes[c] a (blocks_h, blocks_w, 64) int16 array of
-    QUANTISED coefficients in natural order and qtabs a (3, 64) uint16 array in natural order.  Raises JpegUnsupported / JpegError."""
+    QUANTISED coefficients in natural order and qtabs a (3, 64) uint16 array in natural order.  With ``coverage="extended"`` every scan
+    of a progressive file is run into those planes.  Raises JpegUnsupported / JpegError."""
+    flags = _coverage_flags(coverage, "wu.jpeg.entropy_decode")
     lib = _lib.load()
     data = _codec.read(data)
-    info = _parse_bytes(lib, data)
+    info = _parse_bytes(lib, data, flags)
     if not info.supported:
         raise JpegUnsupported(info.reason_name)
     coef = np.empty(info.total_blocks * 64, dtype=np.int16)
     qtabs = np.empty((3, 64), dtype=np.uint16)
     if _entropy_into(lib, data, info, coef.ctypes.data, coef.nbytes, qtabs.ctypes.data) == 1:
-        raise JpegUnsupported("magnitude", f"max block L1 {info.max_block_l1}")
+        raise JpegUnsupported(info.reason_name, f"max block L1 {info.max_block_l1}" if info.reason == 11 else "")
     planes, at = [], 0
     for c in range(info.ncomp):
         nb = info.blocks_h[c] * info.blocks_w[c]
@@ -199,11 +222,20 @@ class GPUJpegDecoder:
     wu_jpeg_reconstruct, then copies the N status words back and waits for them -- ONE host synchronisation per batch, the rule of
     ``wu.png.GPUPngDecoder.finish``: whether the device accepted an image is known only then.  An image it rejects is decoded by Pillow
     into its slot and counted in ``stats`` under the status name ("magnitude", "corrupt-scan").
+
+    ``coverage="extended"`` (default "baseline": everything above, untouched): progressive files and 4:4:0 sampling are decoded natively
+    too and count as ``native``.  The scans of a progressive file are run on the worker thread into the same coefficient blocks, so the
+    device half is the same two launches.  A progressive file whose scans stop short of full precision ("progressive-incomplete") still
+    goes to Pillow, which smooths such a file between blocks.  Host entropy only: with ``entropy="device"`` it is a ValueError.
     """
-    def __init__(self, device="cuda", threads=None, max_staging=8, entropy="host", subseq_bits=None):
+    def __init__(self, device="cuda", threads=None, max_staging=8, entropy="host", subseq_bits=None, coverage="baseline"):
         if entropy not in ("host", "device"):
             raise ValueError(f"GPUJpegDecoder: entropy must be 'host' or 'device', got {entropy!r}")
-        self.entropy = entropy
+        self._flags = _coverage_flags(coverage, "GPUJpegDecoder")
+        if self._flags and entropy == "device":
+            raise ValueError("GPUJpegDecoder: coverage='extended' needs entropy='host' -- the device Huffman walk knows one interleaved "
+                             "baseline scan")
+        self.entropy, self.coverage = entropy, coverage
         self.subseq_bits = DEFAULT_SUBSEQ_BITS if subseq_bits is None else int(subseq_bits)
         if self.subseq_bits % 32 or not 64 <= self.subseq_bits <= 4096:
             raise ValueError(f"GPUJpegDecoder: subseq_bits must be a multiple of 32 in [64, 4096], got {subseq_bits}")
@@ -225,7 +257,7 @@ class GPUJpegDecoder:
     def _open(self, arg):
         i, item = arg
         data = _codec.read(item)
-        info = _parse_bytes(self._lib, data)
+        info = _parse_bytes(self._lib, data, self._flags)
         if info.supported and info.height * info.width <= MAX_NATIVE_PIXELS:
             return data, info, None, None
         # a header may claim any size up to 65535 x 65535: beyond Pillow's own decompression-bomb threshold the file is Pillow's to judge
@@ -268,8 +300,8 @@ class GPUJpegDecoder:
                 rc = _entropy_into(self._lib, data, info, st.ptr + first_block[i] * 128, cap, st.ptr + off["qtab"] + i * 384)
             except JpegError:
                 return _codec.pillow_rgb(data, hb.names[i]), "corrupt-scan"      # Pillow is the arbiter; it raises on a truncated file
-            if rc == 1:
-                return _codec.pillow_rgb(data, hb.names[i]), "magnitude"
+            if rc == 1:                                               # "magnitude", or "progressive-incomplete" / "qtable16" of a progressive file
+                return _codec.pillow_rgb(data, hb.names[i]), info.reason_name
             return None, None
 
         results = list(self._pool.map(decode, range(n)))
