@@ -1002,6 +1002,64 @@ int wu_colour_ot_step(double* state, int nimg, int n, const double* palette_keys
 int wu_colour_ot_store(const double* state, long long first, int nimg, void* y, long long ys_r, long long ys_n, long long ys_c,
                        long long ys_h, long long ys_w, int dtype, int B, int H, int W, double lo, double span, int round_int, void* stream);
 
+/* ---- Regraining (wu/colour.py; Pitie, Kokaram, Dahyot, CVIU 2007, section 5): keep the transferred colours, take the original's gradients -----
+ * On states as wu_colour_ot_load writes them: `state` (nimg, 3, n) holds the transfer IT (unclipped) on entry and the result IR on return,
+ * `original` (nimg, 3, n) the original I0, n = H W <= 2^21.  fp64, every operation rounded on its own, no FMA; tests/_regrain_ref.py restates
+ * it and the result is bit-identical.  sh(a, dy, dx)(y, x) = a(clamp(y + dy), clamp(x + dx)): every neighbour read clamps at the image edge.
+ *   levels   level 0 is H x W; level l + 1 exists iff l + 1 < n_iters and ceil(h_l / 2) > min_side and ceil(w_l / 2) > min_side, and has
+ *            those ceilings as its size.  wu_colour_regrain_levels applies the rule on the host (0 for arguments out of range: H, W >= 1,
+ *            1 <= n_iters <= 6, min_side >= 0); wu_colour_regrain takes the COUNT, 1..6, and halves (rounding up) that many times.
+ *   down     per axis (a[2d] + a[min(2d + 1, last)]) * 0.5, rows first, then columns.
+ *   up       per axis a[d / 2] * 0.75 + a[o] * 0.25, o = d / 2 - 1 for even d and d / 2 + 1 for odd d, clamped; rows first, then columns.
+ *   rec(IR, I0, IT, l): if level l + 1 exists, c0 = down(IR), c1 = rec(c0, down(I0), down(IT), l + 1), IR = IR + up(c1 - c0); then
+ *            IR = solve(IR, I0, IT, iters[l], l).  The top call starts from IR = IT.  A coarse-grid CORRECTION: IR is not replaced.
+ *   solve    gx = sh(I0, 0, +1) - sh(I0, 0, -1), gy = sh(I0, +1, 0) - sh(I0, -1, 0); q_c = gx_c gx_c + gy_c gy_c; dI = sqrt((q_0 + q_1) + q_2);
+ *            psi = min((256 dI) / 5, 1); phi = (30 * 2^-l) / (1 + (10 dI) / smoothness); for the neighbours j = up (-1, 0), down (+1, 0),
+ *            left (0, -1), right (0, +1): phi_j = (sh(phi, j) + phi) * 0.5; den = ((((psi + phi_1) + phi_2) + phi_3) + phi_4) + 2^-52;
+ *            b = (((psi IT + phi_1 (I0 - sh(I0, 1))) + phi_2 (I0 - sh(I0, 2))) + phi_3 (..)) + phi_4 (..) per channel; one iteration
+ *            (Jacobi: every read is of the previous iterate): a = (((b + phi_1 sh(IR, 1)) + phi_2 sh(IR, 2)) + phi_3 sh(IR, 3)) + phi_4 sh(IR, 4),
+ *            IR = (a / den) * 0.8 + 0.2 * IR.  The weights are shared by the three channels.
+ * `iters_host` is a HOST array of `levels` counts, finest level first, each in 1..2^20.  smoothness > 0.  The result is not clipped.
+ * workspace: wu_colour_regrain_workspace_bytes(nimg, H, W, levels), 0 for anything out of range (133 bytes per pixel and image at four
+ * levels).  No atomics, no sum across threads: two runs, any split of the images into calls and any tile size give the same bytes.
+ * Stream-ordered, caller-owned buffers, no allocation, no synchronisation; arguments are refused before any launch. */
+size_t wu_colour_regrain_workspace_bytes(int nimg, int H, int W, int levels);
+int wu_colour_regrain_levels(int H, int W, int n_iters, int min_side);
+int wu_colour_regrain(double* state, const double* original, int nimg, int H, int W, int levels, const int* iters_host, double smoothness,
+                      void* workspace, void* stream);
+
+/* ---- Linear colour maps (wu/colour.py): mean / sigma transfer (Reinhard et al. 2001) and the Monge-Kantorovich map (Pitie & Kokaram 2007) ---
+ *   wu_colour_moments       nsets point sets of n points: channel c of point i of set s is points[s 3 n + i stride_point + c stride_channel];
+ *                           (stride_point, stride_channel) is (1, n) for the planar state (nimg, 3, n) or (3, 1) for palettes (C, P, 3).
+ *                           moments_out (nsets, 12): mu (3), then the 3 x 3 covariance, row-major and symmetric.  Two passes: mu = S / n, then
+ *                           Sigma_ab = (sum_i (s_ia - mu_a) (s_ib - mu_b)) / n for a <= b (the population form: n = 1 gives 0).
+ *                           THE ORDER OF EVERY SUM depends on n alone: with the addends padded by +0.0 to a multiple of 4096, chunk k holds
+ *                           addends 4096 k .. 4096 k + 4095; in a chunk, lane t (0..255) adds addends t, t + 256, .., t + 3840 in that order
+ *                           to +0.0, and the 256 lanes are folded by v[t] = v[t] + v[t + s] for s = 128, 64, .., 1; the chunk sums, padded
+ *                           by +0.0 to a multiple of 256, go the same way: lane t adds chunk sums t, t + 256, .. in order, then the fold.
+ *                           workspace: wu_colour_moments_workspace_bytes(nsets, n) (0 out of range: 1 <= nsets <= 65535, 1 <= n <= 2^21).
+ *   wu_colour_linear_apply  s <- mu_t + A (s - mu_s) on every state v, with (mu_s, Sigma_s) = state_moments[v] and (mu_t, Sigma_t) =
+ *                           palette_moments[classes[v]] (a DEVICE array; an image with a class outside 0..npal-1 is left unchanged):
+ *                           d = s - mu_s, s_c = ((A_c0 d_0 + A_c1 d_1) + A_c2 d_2) + mu_t_c.
+ *                           WU_COLOUR_MEANSTD: A = diag(sqrt(Sigma_t_cc / max(Sigma_s_cc, eps_var))).
+ *                           WU_COLOUR_MKL: A = Si ((S Sigma_t) S)^(1/2) Si, S = f(Sigma_s) with sqrt(max(lambda, eps_var)), Si with its
+ *                           reciprocal 1 / sqrt(max(lambda, eps_var)), the inner root with sqrt(max(lambda, 0)).
+ *                           f(M) = V diag(f) V^T from a cyclic Jacobi on M's upper triangle: exactly 8 sweeps over (p, q) = (0,1), (0,2), (1,2),
+ *                           a rotation skipped when a_pq == 0, else theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| +
+ *                           sqrt(theta theta + 1)) with sign(0) = +1, c = 1 / sqrt(t t + 1), s = t c; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0,
+ *                           (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq), and for every row i of V (v_ip, v_iq) = (c v_ip - s v_iq,
+ *                           s v_ip + c v_iq).  Entry (i, j), i <= j, of f(M) is ((V_i0 f_0) V_j0 + (V_i1 f_1) V_j1) + (V_i2 f_2) V_j2, mirrored;
+ *                           a matrix product entry is (x_i0 y_0j + x_i1 y_1j) + x_i2 y_2j.  No trigonometry: tests/_regrain_ref.py gives
+ *                           the same bits.  The map is formed on the device: nothing is read back.
+ * fp64, no FMA, no atomics.  Stream-ordered, caller-owned buffers, no allocation, no synchronisation. */
+#define WU_COLOUR_MEANSTD 0
+#define WU_COLOUR_MKL 1
+size_t wu_colour_moments_workspace_bytes(int nsets, int n);
+int wu_colour_moments(const double* points, long long stride_point, long long stride_channel, int nsets, int n, double* moments_out,
+                      void* workspace, void* stream);
+int wu_colour_linear_apply(double* state, int nimg, int n, const double* state_moments, const double* palette_moments, int npal,
+                           const int* classes, int mode, double eps_var, void* stream);
+
 /* layout helpers for the module boundary: NHWC `dtype` <-> NCHW fp32 (feature maps returned by
  * SNDisc.forward, disc.py:38; gradients flowing back into them). */
 int wu_nhwc_to_nchw_f32(const void* x, int ldx, float* y_nchw, int N, int H, int W, int C, int dtype, void* stream);

@@ -197,6 +197,12 @@ SIGNATURES = {
     "wu_colour_ot_palette_keys": (I, [P, I, I, P, P, P, P]),
     "wu_colour_ot_step": (I, [P, I, I, P, I, I, P, P, c_double, P, P]),
     "wu_colour_ot_store": (I, [P, ctypes.c_longlong, I, P] + [ctypes.c_longlong] * 5 + [I, I, I, I, c_double, c_double, I, P]),
+    "wu_colour_regrain_workspace_bytes": (SZ, [I, I, I, I]),
+    "wu_colour_regrain_levels": (I, [I, I, I, I]),
+    "wu_colour_regrain": (I, [P, P, I, I, I, I, P, c_double, P, P]),
+    "wu_colour_moments_workspace_bytes": (SZ, [I, I]),
+    "wu_colour_moments": (I, [P, ctypes.c_longlong, ctypes.c_longlong, I, I, P, P, P]),
+    "wu_colour_linear_apply": (I, [P, I, I, P, P, I, P, I, c_double, P]),
     "wu_lpips_tile_pixels": (I, []),
     "wu_lpips_workspace_bytes": (SZ, [I, I, I, I, I]),
     "wu_lpips_input": (I, [P] + [ctypes.c_longlong] * 4 + [I, I, I, I, c_float, c_float, P, I, P]),
