@@ -960,6 +960,14 @@ int wu_ssim_pairs(const void* x, long long xs_n, long long xs_c, long long xs_h,
  *   wu_swd_sort_columns  the sort of wu_swd_project_sort on its own: every row of keys (ncols, m), finite doubles, ascending and in place;
  *                        workspace: wu_swd_workspace_bytes(m, ncols, ncols) bytes.  Same ranges.
  *   wu_swd_distance      w[j] = mean_i |a[j][i] - b[j][i]| of two (ndirs, m) arrays, a fixed-order tree sum per direction.
+ *   wu_swd_distance_unequal
+ *                        a (ndirs, m1), b (ndirs, m2), rows ascending: w[j] = the exact W1 of the two empirical distributions, the integral
+ *                        of |Fa^-1(t) - Fb^-1(t)| over t in [0, 1].  With x the longer row (ml keys), y the shorter (ms <= ml; x = a when
+ *                        m1 == m2) and t in units of 1 / (ml ms), x_i owns [i ms, (i + 1) ms) and y_j owns [j ml, (j + 1) ml); in int64,
+ *                        lo = i ms, hi = lo + ms, j0 = lo / ml, j1 = (hi - 1) / ml <= j0 + 1, cut = (j0 + 1) ml, w0 = min(hi, cut) - lo,
+ *                        w1 = hi - min(hi, cut); w[j] = (sum_i w0 |x_i - y_j0| + w1 |x_i - y_j1|) / (double)(m1 m2): thread t of 256 adds
+ *                        the two terms of i = t, t + 256, .. in that order (the second also when w1 == 0), then the fixed-order tree sum of
+ *                        wu_swd_distance.  No search, no atomics; W(a, b) and W(b, a) are the same bits.  1 <= m1, m2 <= 2^21.
  * The *_workspace_bytes functions return 0 for anything out of range. */
 int wu_swd_sort_block(void);
 size_t wu_swd_pyramid_workspace_bytes(int N, int H, int W, int levels, int P);
@@ -972,6 +980,7 @@ int wu_swd_project_sort(const float* desc, int m, const float* dirs, int ndirs, 
                         void* stream);
 int wu_swd_sort_columns(double* keys, int m, int ncols, void* workspace, void* stream);
 int wu_swd_distance(const double* a, const double* b, int m, int ndirs, double* w, void* stream);
+int wu_swd_distance_unequal(const double* a, int m1, const double* b, int m2, int ndirs, double* w, void* stream);
 
 /* ---- Colour-transfer baselines (wu/colour.py): histogram matching and sliced optimal transport of pixel colours --------------------------
  * A "virtual image" g = r B + b is input image b on its way to target r; its state is (3, n) fp64 in [0, 1] units, n = H W.  `first` is the

@@ -11,7 +11,18 @@ matmul, torch.sort(dim=1), mean absolute difference.
 One JSON line per config: the median over the timed calls (device events around one whole call, inputs resident), all the times, the peak
 device memory above the resident inputs (torch.cuda.max_memory_allocated), the library's launches (counted by `launches`, which mirrors the
 launcher's loops) and the composition's torch op calls (each at least one launch), and how far the two results lie apart.  One config per
-process keeps a config's allocator state out of the next one's peak."""
+process keeps a config's allocator state out of the next one's peak.
+
+    python scratch/bench_swd.py --unequal kernel320k [--steps 7] [--warmup 3]
+
+  kernel320k / kernel1m   wu_swd_distance_unequal alone on sorted (512, 64 000) against (512, 320 000) / (512, 1 048 576) float64 columns,
+                          against the closed form out of torch ops (int64 arange, two gathers, abs, multiply, sum(1))
+  split5x   500 against 2 500 images of 3 x 224 x 224: unequal="exact", the seeded 500-subset rule, the torch composition
+  refs5     SlicedWasserstein.compute() of five rows of 500 outputs: five reference banks of 2 500 images, one shared bank, today's inputs
+  spread    the subset rule over seeds 0-4 beside the exact value on one pair of sets
+
+The candidates of one --unequal measurement alternate inside every round (`timed_alternating`); a candidate slower than its baseline is
+marked LOSS."""
 import argparse
 import json
 import os
@@ -206,13 +217,224 @@ def bench_sort(name, a):
                       "device": torch.cuda.get_device_name(0)}), flush=True)
 
 
+# ----------------------------------------------------------------------------------------------
+# --unequal: sets of unequal size (wu_swd_distance_unequal, unequal="exact", DescriptorBank, SlicedWasserstein(reference=))
+# ----------------------------------------------------------------------------------------------
+UNEQUAL = {"kernel320k": (64000, 320000), "kernel1m": (64000, 1 << 20), "split5x": (500, 2500), "refs5": (500, 2500), "spread": (500, 2500)}
+
+
+def timed_alternating(fns, steps, warmup):
+    """{name: (median ms, [all ms])}: the candidates take turns inside every round, so that drift of the machine hits all alike."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(steps):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[k].append(e0.elapsed_time(e1))
+    return {k: (round(float(np.median(v)), 3), [round(t, 3) for t in v]) for k, v in times.items()}
+
+
+def torch_w1_unequal(x, y):
+    """The closed form out of torch ops on sorted (ndirs, ml) and (ndirs, ms <= ml) float64 columns: int64 arange, two gathers, abs,
+    multiply, sum(1)."""
+    ml, ms = x.shape[1], y.shape[1]
+    lo = op(torch.arange(ml, device=x.device, dtype=torch.int64) * ms)
+    hi = op(lo + ms)
+    j0 = op(lo // ml)
+    j1 = op(op(hi - 1) // ml)
+    mid = op(torch.minimum(hi, op(op(j0 + 1) * ml)))
+    w0, w1 = op(op(mid - lo).double()), op(op(hi - mid).double())
+    t0 = op(w0 * op(op(x - op(y[:, j0])).abs()))
+    t1 = op(w1 * op(op(x - op(y[:, j1])).abs()))
+    return op(op(op(t0 + t1).sum(1)) / float(ml * ms))
+
+
+def _report(out, name, times, baseline):
+    for k, (ms, all_ms) in times.items():
+        out[f"{k}_ms_median"], out[f"{k}_ms_all"] = ms, all_ms
+    for k in times:
+        if k != baseline:
+            out[f"{k}_vs_{baseline}"] = ("LOSS " if times[k][0] > times[baseline][0] else "") + f"{times[baseline][0] / times[k][0]:.2f}x"
+    out["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(out), flush=True)
+
+
+def bench_unequal_kernel(name, a):
+    from wu import _lib
+    from wu.layout import stream_ptr
+    ms_, ml_ = UNEQUAL[name]
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(2)
+    y = torch.sort(torch.randn((NDIRS, ms_), dtype=torch.float64, device=dev, generator=gen), dim=1)[0]
+    x = torch.sort(torch.randn((NDIRS, ml_), dtype=torch.float64, device=dev, generator=gen) * 0.8 + 0.1, dim=1)[0]
+    w = torch.empty(NDIRS, dtype=torch.float64, device=dev)
+
+    def fused():
+        _lib.call("wu_swd_distance_unequal", y.data_ptr(), ms_, x.data_ptr(), ml_, NDIRS, w.data_ptr(), stream_ptr())
+        return w
+
+    def comp():
+        return torch_w1_unequal(x, y)
+
+    OPS[0] = 0
+    ref = comp()
+    ops = OPS[0]
+    rel = float(((fused() - ref).abs() / ref).max())
+    times = timed_alternating({"fused": fused, "torch": comp}, a.steps, a.warmup)
+    nbytes = 8 * NDIRS * (ml_ + ms_)
+    out = {"config": name, "ms": ms_, "ml": ml_, "ndirs": NDIRS, "steps": a.steps, "warmup": a.warmup, "torch_op_calls": ops,
+           "max_rel_diff": rel, "bytes_read_once": nbytes, "fused_read_GBps": round(nbytes / times["fused"][0] / 1e6, 1),
+           "fused_peak_extra_bytes": peak_extra(fused), "torch_peak_extra_bytes": peak_extra(comp)}
+    _report(out, name, times, "torch")
+
+
+def _images(n, size, noise, seed, dev, chunk=500):
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    parts = []
+    for i in range(0, n, chunk):
+        k = min(chunk, n - i)
+        coarse = torch.rand((k, size // 8, size // 8, 3), generator=gen, device=dev)
+        x = coarse.repeat_interleave(8, 1).repeat_interleave(8, 2) * (1 - noise) + noise * torch.rand((k, size, size, 3), generator=gen, device=dev)
+        parts.append((x * 255).round().to(torch.uint8))
+    return torch.cat(parts).permute(0, 3, 1, 2)                                       # NHWC storage, read through its strides
+
+
+def bench_unequal_split(name, a):
+    """500 against 2 500 images: exact, against the seeded 500-subset of the larger set (what the command line did), against the torch
+    composition with the closed form as its last stage."""
+    from wu import paired, swd
+    na, nb = UNEQUAL[name]
+    size, dev = 224, torch.device("cuda:0")
+    xa, xb = _images(na, size, 0.3, 0, dev), _images(nb, size, 0.5, 1, dev)
+    levels = swd.default_levels(size, size)
+    shapes = swd.check_levels(size, size, levels)
+    pos, dirs = swd.draw(0, levels, shapes, nb, P, NDIRS)
+    pos_d, dirs64 = torch.from_numpy(pos).to(dev), torch.from_numpy(dirs).to(dev).double()
+    scale, shift, _ = paired.range_mapping("uint8")
+    keep = torch.from_numpy(np.sort(np.random.RandomState(0).permutation(nb)[:na])).to(dev)
+
+    def exact():
+        da, db = swd.descriptors(xa, pos[:, :na], "uint8", levels), swd.descriptors(xb, pos, "uint8", levels)
+        return swd.distances(da, db, dirs, unequal="exact")
+
+    def subset():
+        da, db = swd.descriptors(xa, pos[:, :na], "uint8", levels), swd.descriptors(xb[keep], pos[:, :na], "uint8", levels)
+        return swd.distances(da, db, dirs)
+
+    def comp():
+        da = torch_descriptors(xa, pos_d[:, :na], levels, scale, shift)
+        db = torch_descriptors(xb, pos_d, levels, scale, shift)
+        out = []
+        for p, q in zip(da, db):
+            def cols(dsc):
+                v = dsc.double().view(-1, 3, 49)
+                mu = v.mean((0, 2), keepdim=True)
+                sd = ((v - mu) ** 2).mean((0, 2), keepdim=True).sqrt()
+                return torch.sort(dirs64 @ ((v - mu) / sd).float().view(-1, 147).double().t(), dim=1)[0]
+            out.append(torch_w1_unequal(cols(q), cols(p)).mean())
+        return torch.stack(out)
+
+    fns = {"exact": exact, "subset": subset}
+    if not a.no_torch:
+        fns["torch"] = comp
+    ref = exact()
+    out = {"config": name, "images": [na, nb], "size": size, "levels": levels, "P": P, "ndirs": NDIRS, "m": [na * P, nb * P],
+           "steps": a.steps, "warmup": a.warmup, "exact_x1e3": [round(float(v) * 1e3, 4) for v in ref.tolist()],
+           "subset_x1e3": [round(float(v) * 1e3, 4) for v in subset().tolist()]}
+    if not a.no_torch:
+        out["max_rel_diff_exact_torch"] = float(((comp() - ref).abs() / ref).max())
+    times = timed_alternating(fns, a.steps, a.warmup)
+    out.update({f"{k}_peak_extra_bytes": peak_extra(fn) for k, fn in fns.items()})
+    for k in ("subset", "torch"):
+        if k in times:
+            out[f"exact_vs_{k}"] = ("LOSS " if times["exact"][0] > times[k][0] else "") + f"{times[k][0] / times['exact'][0]:.2f}x"
+    for k, (ms, all_ms) in times.items():
+        out[f"{k}_ms_median"], out[f"{k}_ms_all"] = ms, all_ms
+    out["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(out), flush=True)
+
+
+def bench_unequal_refs(name, a):
+    """compute() of SlicedWasserstein over five rows of 500 outputs: each row against its own reference bank of 2 500 images
+    (reference=[..]), against one bank shared by the five rows (sorted once per direction group), and today's five rows against the 500
+    inputs."""
+    from wu import swd
+    from wu.evaluate import SlicedWasserstein
+    na, nb = UNEQUAL[name]
+    size, dev, rows = 224, torch.device("cuda:0"), 5
+    banks = []
+    for r in range(rows):
+        bank = swd.DescriptorBank(P=P, repeats=1, dirs_per_repeat=NDIRS, value_range="uint8")
+        for i in range(0, nb, 500):
+            bank.add(_images(500, size, 0.35 + 0.05 * r, 100 + 10 * r + i // 500, dev))
+        bank.descriptors()
+        banks.append(bank)
+    xa = _images(na, size, 0.3, 0, dev)
+    fakes = torch.stack([_images(na, size, 0.35 + 0.05 * r, 50 + r, dev) for r in range(rows)])
+    accs = {"per_class_refs": SlicedWasserstein(P=P, repeats=1, dirs_per_repeat=NDIRS, value_range="uint8", reference=banks),
+            "one_shared_ref": SlicedWasserstein(P=P, repeats=1, dirs_per_repeat=NDIRS, value_range="uint8", reference=banks[0]),
+            "inputs_today": SlicedWasserstein(P=P, repeats=1, dirs_per_repeat=NDIRS, value_range="uint8")}
+    upd = {}
+    for k, acc in accs.items():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(0, na, 100):
+            acc.update(xa[i:i + 100], fakes[:, i:i + 100])
+        e1.record()
+        torch.cuda.synchronize()
+        upd[k] = round(e0.elapsed_time(e1), 3)
+    times = timed_alternating({k: acc.compute for k, acc in accs.items()}, a.steps, a.warmup)
+    out = {"config": name, "rows": rows, "outputs_per_row": na, "reference_images": nb, "size": size, "P": P, "ndirs": NDIRS,
+           "steps": a.steps, "warmup": a.warmup, "update_ms_once_unwarmed": upd,
+           "mean_x1e3": {k: [round(r.mean, 4) for r in acc.compute()] for k, acc in accs.items()}}
+    out.update({f"{k}_peak_extra_bytes": peak_extra(acc.compute) for k, acc in accs.items()})
+    _report(out, name, times, "inputs_today")
+
+
+def bench_unequal_spread(name, a):
+    """The argument for the feature: on one pair of sets, the subset rule over seeds 0-4 (the seed draws the subset, the positions and the
+    directions, as the command line does) beside the exact value over the same seeds (positions and directions only)."""
+    from wu import swd
+    na, nb = UNEQUAL[name]
+    size, dev = 224, torch.device("cuda:0")
+    xa, xb = _images(na, size, 0.3, 0, dev), _images(nb, size, 0.5, 1, dev)
+    out = {"config": name, "images": [na, nb], "size": size, "P": P, "ndirs": NDIRS, "subset": {}, "exact": {}, "subset_fixed_draws": {}}
+    for seed in range(5):
+        keep = torch.from_numpy(np.sort(np.random.RandomState(seed).permutation(nb)[:na])).to(dev)
+        kw = dict(P=P, repeats=1, dirs_per_repeat=NDIRS, value_range="uint8")
+        out["subset"][seed] = [round(v, 4) for v in swd.swd(xa, xb[keep], seed=seed, **kw).levels]
+        out["subset_fixed_draws"][seed] = [round(v, 4) for v in swd.swd(xa, xb[keep], seed=0, **kw).levels]
+        out["exact"][seed] = [round(v, 4) for v in swd.swd(xa, xb, seed=seed, unequal="exact", **kw).levels]
+    for k in ("subset", "subset_fixed_draws", "exact"):
+        v = np.array(list(out[k].values()))
+        out[f"{k}_min_max_per_level"] = [[float(v[:, l].min()), float(v[:, l].max())] for l in range(v.shape[1])]
+        out[f"{k}_mean_min_max"] = [round(float(v.mean(1).min()), 4), round(float(v.mean(1).max()), 4)]
+    out["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--config", required=True, choices=list(CONFIGS))
+    ap.add_argument("--config", choices=list(CONFIGS))
+    ap.add_argument("--unequal", choices=list(UNEQUAL), help="a measurement on sets of unequal size instead of --config: the distance kernel "
+                    "alone (kernel320k, kernel1m), 500 against 2 500 images (split5x), five reference banks (refs5), the subset rule's spread")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch composition (the full configs)")
     a = ap.parse_args()
+    if (a.config is None) == (a.unequal is None):
+        ap.error("give --config or --unequal")
+    if a.unequal:
+        {"kernel320k": bench_unequal_kernel, "kernel1m": bench_unequal_kernel, "split5x": bench_unequal_split, "refs5": bench_unequal_refs,
+         "spread": bench_unequal_spread}[a.unequal](a.unequal, a)
+        return
     (bench_sort if a.config.startswith("sort") else bench_full)(a.config, a)
 
 

@@ -15,7 +15,10 @@
 //                          with +inf up to the next power of two only), then merge passes over global memory in
 //                          which a workgroup finds its tile of the merge path by bisection, stages it in LDS, and every thread merges
 //                          kSwdMergePer keys there;
-//   * swd_distance_kernel  a workgroup per direction: mean_i |a_i - b_i| from a fixed-order tree sum.
+//   * swd_distance_kernel  a workgroup per direction: mean_i |a_i - b_i| from a fixed-order tree sum;
+//   * swd_distance_unequal_kernel
+//                          the same for two columns of unequal length: the exact W1 of the two empirical distributions as a closed-form
+//                          walk over the longer column, at most two keys of the shorter one per key, the same fixed-order sum.
 // No atomics anywhere, every sum in one order that depends on the sizes alone: the same inputs give the same bits, whatever dir_chunk.
 #include <math.h>
 
@@ -388,6 +391,41 @@ __global__ __launch_bounds__(256) void swd_distance_kernel(const double* a, cons
     if (threadIdx.x == 0) w[blockIdx.x] = (((sW[0] + sW[1]) + sW[2]) + sW[3]) / (double)m;
 }
 
+// one workgroup per direction, two columns of unequal length: x is the LONGER one (ml keys), y the shorter (ms <= ml).  W1 is the integral
+// of |Fx^-1(t) - Fy^-1(t)| over t; with t in units of 1 / (ml ms), x_i owns [i ms, (i + 1) ms) and y_j owns [j ml, (j + 1) ml), and an
+// interval of length ms <= ml meets at most two of y's: j0 = i ms / ml over the first w0 = min(ms, ml - i ms % ml) units, j0 + 1 over the
+// other w1 = ms - w0.  Thread t takes i = t, t + 256, ..: quotient and remainder of i ms by ml are carried from one i to the next (all
+// int64: ml ms reaches 2^42), so the loop divides once.  The second term is always added (+0.0 when w1 == 0, then from y_j0 again);
+// lanes and waves as swd_distance_kernel.
+__global__ __launch_bounds__(256) void swd_distance_unequal_kernel(const double* x, long long ml, const double* y, long long ms, double* w) {
+    __shared__ double sW[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double* px = x + (long long)blockIdx.x * ml;
+    const double* py = y + (long long)blockIdx.x * ms;
+    const long long step = 256 * ms, qs = step / ml, rs = step % ml;
+    long long i = threadIdx.x;
+    long long j0 = i * ms / ml, rem = i * ms % ml;        // i ms = j0 ml + rem
+    double s = 0.0;
+    for (; i < ml; i += 256) {
+        const long long left = ml - rem;                  // units of x_i's interval up to the end of y_j0's
+        const long long n0 = ms < left ? ms : left;
+        const long long j1 = ms > left ? j0 + 1 : j0;     // (i + 1) ms - 1 < ml ms: j1 <= ms - 1
+        const double xi = px[i];
+        s = s + (double)n0 * fabs(xi - py[j0]);
+        s = s + (double)(ms - n0) * fabs(xi - py[j1]);
+        j0 += qs;
+        rem += rs;
+        if (rem >= ml) {
+            rem -= ml;
+            ++j0;
+        }
+    }
+    s = wave_sum_f64(s);
+    if (lane == 0) sW[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) w[blockIdx.x] = (((sW[0] + sW[1]) + sW[2]) + sW[3]) / (double)(ml * ms);
+}
+
 // sizes of every level and the offsets (in doubles) of G_1.. in the workspace; false for anything out of range
 struct SwdPlan {
     int h[kSwdMaxLevels], w[kSwdMaxLevels];
@@ -586,5 +624,18 @@ extern "C" int wu_swd_distance(const double* a, const double* b, int m, int ndir
     WU_REQUIRE(a && b && w, "wu_swd_distance: NULL pointer");
     hipLaunchKernelGGL(swd_distance_kernel, dim3(ndirs), dim3(256), 0, (hipStream_t)stream, a, b, m, w);
     WU_LAUNCH_CHECK("swd_distance_kernel");
+    return 0;
+}
+
+extern "C" int wu_swd_distance_unequal(const double* a, int m1, const double* b, int m2, int ndirs, double* w, void* stream) {
+    WU_REQUIRE(m1 >= 1 && m1 <= kSwdMaxM && m2 >= 1 && m2 <= kSwdMaxM, "wu_swd_distance_unequal: m1 %d / m2 %d must be in 1..%d", m1, m2,
+               kSwdMaxM);
+    WU_REQUIRE(ndirs >= 1 && ndirs <= kSwdMaxDirs, "wu_swd_distance_unequal: ndirs %d must be in 1..%d", ndirs, kSwdMaxDirs);
+    WU_REQUIRE(a && b && w, "wu_swd_distance_unequal: NULL pointer");
+    // the walk is always over the longer column, so that W(a, b) and W(b, a) are the same bits
+    const bool swap = m2 > m1;
+    hipLaunchKernelGGL(swd_distance_unequal_kernel, dim3(ndirs), dim3(256), 0, (hipStream_t)stream, swap ? b : a,
+                       (long long)(swap ? m2 : m1), swap ? a : b, (long long)(swap ? m1 : m2), w);
+    WU_LAUNCH_CHECK("swd_distance_unequal_kernel");
     return 0;
 }

@@ -177,13 +177,19 @@ class SlicedWasserstein:
     descriptors of the batch are gathered and kept on the device, 75 KB per image and level, no host synchronisation.  Image i of the
     stream gets the positions ``wu.swd.draw`` gives image i, so any split into batches equals one call on the concatenation, bit for bit.
     ``compute()`` normalises, projects, sorts and reports: a ``wu.swd.SWDResult`` (per-level values x 1e3, finest level first, and their
-    mean), or a list of R of them when ``fake`` came with rows."""
+    mean), or a list of R of them when ``fake`` came with rows.
+    ``reference``: a ``wu.swd.DescriptorBank``, or a list of R of them, one per row -- the photographs of the target class, say, of any
+    count.  ``update`` then gathers only ``fake``, and ``compute()`` compares row r's outputs with ``reference[r]`` (or with the one bank)
+    by the exact W1 for unequal counts (``wu.swd.compare`` of the row's outputs and that bank, bit for bit); a bank that serves several
+    rows is normalised and sorted once per direction group, not once per row.  The banks must share this accumulator's P, seed, number
+    of directions, levels, image size and value-range mapping (ValueError in ``compute``).  ``None``: as before."""
 
-    def __init__(self, P=128, repeats=4, dirs_per_repeat=128, seed=0, value_range=(-1, 1), levels=None, dir_chunk=0):
+    def __init__(self, P=128, repeats=4, dirs_per_repeat=128, seed=0, value_range=(-1, 1), levels=None, dir_chunk=0, reference=None):
         self.P, self.ndirs, self.seed = int(P), int(repeats) * int(dirs_per_repeat), seed
         self.value_range, self.levels, self.dir_chunk = value_range, levels, int(dir_chunk)
         self.count, self.shape, self.rows = 0, None, None
         self.real, self.fake = [], []
+        self.reference = list(reference) if isinstance(reference, (list, tuple)) else reference
 
     @torch.no_grad()
     def update(self, real, fake):
@@ -203,21 +209,42 @@ class SlicedWasserstein:
             raise ValueError(f"SlicedWasserstein.update: {h} x {w} with rows {rows} after {self.shape[0]} x {self.shape[1]} with rows {self.rows}")
         shapes = swd.check_levels(h, w, self.levels)
         pos, _ = swd.draw(self.seed, self.levels, shapes, b, self.P, self.ndirs, first=self.count)
-        self.real.append(swd.descriptors(real, pos, self.value_range, self.levels))
+        if self.reference is None:
+            self.real.append(swd.descriptors(real, pos, self.value_range, self.levels))
         self.fake.append([swd.descriptors(f, pos, self.value_range, self.levels) for f in (fake if rows is not None else fake[None])])
         self.count += b
 
     def compute(self):
         from . import swd
-        if not self.real:
+        if not self.fake:
             raise RuntimeError("no batch has been added yet")
         shapes = swd.check_levels(*self.shape, self.levels)
         _, dirs = swd.draw(self.seed, self.levels, shapes, 1, 1, self.ndirs)
+        if self.reference is not None:
+            return self._against_reference(dirs)
         real = [torch.cat([part[l] for part in self.real]) for l in range(self.levels)]
         out = []
         for r in range(len(self.fake[0])):
             fake = [torch.cat([part[r][l] for part in self.fake]) for l in range(self.levels)]
             out.append(swd.report(swd.distances(real, fake, dirs, self.dir_chunk).tolist()))
+        return out if self.rows is not None else out[0]
+
+    def _against_reference(self, dirs):
+        from . import swd
+        from .paired import range_mapping
+        nrows = len(self.fake[0])
+        banks = self.reference if isinstance(self.reference, list) else [self.reference] * nrows
+        if len(banks) != nrows:
+            raise ValueError(f"SlicedWasserstein: {len(banks)} reference banks for {nrows} rows")
+        mine = {"P": self.P, "seed": self.seed, "ndirs": self.ndirs, "levels": self.levels, "image size": self.shape,
+                "value-range mapping": tuple(range_mapping(self.value_range)[:2])}
+        out = [None] * nrows
+        for bank in {id(b): b for b in banks}.values():             # each distinct bank once, with all the rows it serves
+            swd.check_comparable(mine, bank.signature(), "SlicedWasserstein(reference=)")
+            rows = [r for r in range(nrows) if banks[r] is bank]
+            fakes = [[torch.cat([part[r][l] for part in self.fake]) for l in range(self.levels)] for r in rows]
+            for r, values in zip(rows, swd.distances_to_rows(bank.descriptors(), fakes, dirs, self.dir_chunk).tolist()):
+                out[r] = swd.report(values)
         return out if self.rows is not None else out[0]
 
 

@@ -6,7 +6,10 @@ Pixels only: no pretrained network, no feature extractor.
     d = descriptors(images, positions)                  # per level, (N * P, 147) float32 CUDA
     dn, mu, sigma = normalize(d[0])
     w = sliced_wasserstein(dn_a, dn_b, dirs)            # (ndirs,) float64 CUDA
+    r = swd(images_a, images_b, unequal="exact")        # (Na, 3, H, W) against (Nb, 3, H, W): the exact W1 per direction, nothing dropped
+    r = compare(DescriptorBank.from_dir(DIR_A), DescriptorBank.from_dir(DIR_B))
     python -m wu.swd DIR_A DIR_B [--size S [--filter bicubic]] [--patches 128] [--repeats 4] [--dirs 128] [--seed 0] [--gpu-decode]
+                                 [--unequal subset|exact]
 
 Semantics, in full (tests/_swd_ref.py restates them in numpy).  All pyramid arithmetic in float64, every operation rounded on its own.
 
@@ -42,7 +45,18 @@ Both sets of a comparison use the same positions and directions.
 
 Distance.  For direction j: ``a = sort(D1 @ dir_j)``, ``b = sort(D2 @ dir_j)``, products and sums in float64 on the float32 operands;
 ``w_j = mean_i |a_i - b_i|``; the level's SWD is ``mean_j w_j``.  ``swd`` reports it times 1e3, as PGGAN's tables do, and the mean over
-levels.  ``m1 != m2`` raises.  Inputs must be finite.
+levels.  Inputs must be finite.  ``m1 != m2`` raises unless ``unequal="exact"`` is given; then ``w_j`` is the exact W1 of the two empirical
+distributions, ``integral over t in [0, 1] of |Fa^-1(t) - Fb^-1(t)|``, by this rule.  Let x be the longer sorted column (``ml`` keys) and
+y the shorter (``ms <= ml``), and measure t in units of ``1 / (ml ms)``: ``x_i`` owns ``[i ms, (i + 1) ms)`` and ``y_j`` owns
+``[j ml, (j + 1) ml)``, and an interval of length ``ms <= ml`` meets at most two of y's.  In int64: ``lo = i ms``, ``hi = lo + ms``,
+``j0 = lo // ml``, ``j1 = (hi - 1) // ml`` (``j0`` or ``j0 + 1``), ``cut = (j0 + 1) ml``, ``w0 = min(hi, cut) - lo``,
+``w1 = hi - min(hi, cut)`` (0 exactly when ``j1 == j0``), and ``w_j = (sum_i w0 |x_i - y_j0| + w1 |x_i - y_j1|) / (ml ms)`` with the
+weights converted to float64 (exact) and every product and sum rounded on its own.  No approximation and no search; which set is called a
+or b changes no bit.  Equal counts with ``unequal="exact"`` take the equal-count path and give today's bits (the rule reduces to
+``mean_i |a_i - b_i|`` there).  ``swd(..., unequal="exact")`` takes sets of ``Na`` and ``Nb`` images of one size: positions are one
+``draw`` over ``max(Na, Nb)`` images and image i of either set gets the positions of image i.  ``DescriptorBank`` keeps the raw
+descriptors of a stream of batches (or of a directory, ``from_dir``) and ``compare(bank_a, bank_b)`` is the same number for two banks of
+any two counts; ``wu.evaluate.SlicedWasserstein(reference=bank)`` compares the outputs with such a bank instead of the input batch.
 
 Kernels (csrc/swd.hip): the pyramid keeps only G_1.. in float64 (a third of the input), forms L_l at the gathered pixels only, projects in
 64 x 64 tiles on the fp64 matrix cores, sorts every (direction, set) column with an on-chip bitonic block sort and global merge passes, and
@@ -206,28 +220,49 @@ def sort_columns(keys):
     return keys
 
 
-def sliced_wasserstein(d1, d2, dirs, dir_chunk=0):
-    """(ndirs,) float64 CUDA: ``w_j = mean_i |sort(d1 @ dir_j)_i - sort(d2 @ dir_j)_i|``.  d1, d2 (m, 147) float32 normalised descriptors,
-    dirs (ndirs, 147) float32 (numpy or CUDA).  Directions go through in groups, so the sorted columns of both sets never take more than
-    about ``PAIR_BYTES``; inside a group the library handles ``dir_chunk`` directions per pass (0: its own choice).  Neither changes a bit
-    of the result."""
+def _check_unequal(unequal, what):
+    if unequal not in ("raise", "exact"):
+        raise ValueError(f"{what}: unequal must be \"raise\" or \"exact\", got {unequal!r}")
+
+
+def _one_against_rows(d1, rows, dirs, dir_chunk, what, unequal="exact"):
+    """One (ndirs,) float64 CUDA tensor per element of ``rows``: ``d1`` (m1, 147) against each (m_r, 147) of ``rows``, all normalised
+    float32 descriptors of any counts.  A direction group holds ``PAIR_BYTES // (8 * (m1 + max m_r))`` directions; the columns of ``d1``
+    are sorted once per group, whatever the number of rows.  Equal counts go through wu_swd_distance, the others through
+    wu_swd_distance_unequal."""
     if not torch.is_tensor(dirs):
-        _require_cuda(d1, d2)
+        _require_cuda(d1, *rows)
         dirs = torch.from_numpy(np.ascontiguousarray(dirs, dtype=np.float32)).to(d1.device)
-    d1, d2, dirs = _rows(d1, "sliced_wasserstein"), _rows(d2, "sliced_wasserstein"), _rows(dirs, "sliced_wasserstein")
-    if d1.shape[0] != d2.shape[0]:
-        raise ValueError(f"sliced_wasserstein: {d1.shape[0]} descriptors against {d2.shape[0]}; unequal counts are not supported")
-    m, nd = d1.shape[0], dirs.shape[0]
-    if not (1 <= m <= MAX_M and 1 <= nd <= MAX_DIRS) or dir_chunk < 0:
-        raise ValueError(f"sliced_wasserstein: m {m} (1..{MAX_M}), ndirs {nd} (1..{MAX_DIRS}) or dir_chunk {dir_chunk} out of range")
-    group = max(1, min(nd, PAIR_BYTES // (16 * m)))
-    w = torch.empty(nd, dtype=torch.float64, device=d1.device)
+    d1, rows, dirs = _rows(d1, what), [_rows(r, what) for r in rows], _rows(dirs, what)
+    m1, nd = d1.shape[0], dirs.shape[0]
+    sizes = [m1] + [r.shape[0] for r in rows]
+    if unequal == "raise" and max(sizes) != min(sizes):
+        raise ValueError(f"{what}: {m1} descriptors against {[m for m in sizes[1:] if m != m1][0]}; unequal counts are not supported")
+    if not (1 <= min(sizes) and max(sizes) <= MAX_M and 1 <= nd <= MAX_DIRS) or dir_chunk < 0:
+        raise ValueError(f"{what}: m {sizes} (1..{MAX_M}), ndirs {nd} (1..{MAX_DIRS}) or dir_chunk {dir_chunk} out of range")
+    group = max(1, min(nd, PAIR_BYTES // (8 * (m1 + max(sizes[1:])))))
+    out = [torch.empty(nd, dtype=torch.float64, device=d1.device) for _ in rows]
     with torch.cuda.device(d1.device):
         for j0 in range(0, nd, group):
             a = sorted_projections(d1, dirs[j0:j0 + group], dir_chunk)
-            b = sorted_projections(d2, dirs[j0:j0 + group], dir_chunk)
-            _lib.call("wu_swd_distance", a.data_ptr(), b.data_ptr(), m, a.shape[0], w[j0:].data_ptr(), stream_ptr())
-    return w
+            for d2, w in zip(rows, out):
+                b = sorted_projections(d2, dirs[j0:j0 + group], dir_chunk)
+                if d2.shape[0] == m1:
+                    _lib.call("wu_swd_distance", a.data_ptr(), b.data_ptr(), m1, a.shape[0], w[j0:].data_ptr(), stream_ptr())
+                else:
+                    _lib.call("wu_swd_distance_unequal", a.data_ptr(), m1, b.data_ptr(), d2.shape[0], a.shape[0], w[j0:].data_ptr(),
+                              stream_ptr())
+    return out
+
+
+def sliced_wasserstein(d1, d2, dirs, dir_chunk=0, unequal="raise"):
+    """(ndirs,) float64 CUDA: ``w_j = mean_i |sort(d1 @ dir_j)_i - sort(d2 @ dir_j)_i|``.  d1, d2 (m, 147) float32 normalised descriptors,
+    dirs (ndirs, 147) float32 (numpy or CUDA).  Directions go through in groups, so the sorted columns of both sets never take more than
+    about ``PAIR_BYTES``; inside a group the library handles ``dir_chunk`` directions per pass (0: its own choice).  Neither changes a bit
+    of the result.  ``unequal="exact"``: d1 (m1, 147) and d2 (m2, 147) of any two counts, ``w_j`` the exact W1 of the two sorted columns
+    (the module docstring's rule); equal counts give the same bits as the default."""
+    _check_unequal(unequal, "sliced_wasserstein")
+    return _one_against_rows(d1, [d2], dirs, dir_chunk, "sliced_wasserstein", unequal)[0]
 
 
 def report(level_values):
@@ -236,45 +271,153 @@ def report(level_values):
     return SWDResult(lv, float(np.mean(lv)))
 
 
-def distances(desc_a, desc_b, dirs, dir_chunk=0):
-    """Per level: normalise both sets' raw descriptors, project, sort, and take the mean over directions -> (levels,) float64 CUDA."""
+def distances(desc_a, desc_b, dirs, dir_chunk=0, unequal="raise"):
+    """Per level: normalise both sets' raw descriptors, project, sort, and take the mean over directions -> (levels,) float64 CUDA.
+    ``unequal="exact"``: the two sets may hold different numbers of descriptors."""
+    _check_unequal(unequal, "distances")
     out = []
     for da, db in zip(desc_a, desc_b):
-        out.append(sliced_wasserstein(normalize(da)[0], normalize(db)[0], dirs, dir_chunk).mean())
+        out.append(sliced_wasserstein(normalize(da)[0], normalize(db)[0], dirs, dir_chunk, unequal).mean())
     return torch.stack(out)
 
 
-def swd(images_a, images_b, P=128, repeats=4, dirs_per_repeat=128, seed=0, value_range=(-1, 1), levels=None, dir_chunk=0):
+def distances_to_rows(desc_ref, desc_rows, dirs, dir_chunk=0):
+    """``distances(desc_ref, desc_rows[r], ..., unequal="exact")`` for every r, stacked to (R, levels) float64 CUDA, the same bits: per
+    level the reference set is normalised once and each of its direction groups sorted once, whatever R."""
+    out = []
+    for l, ref in enumerate(desc_ref):
+        ws = _one_against_rows(normalize(ref)[0], [normalize(row[l])[0] for row in desc_rows], dirs, dir_chunk, "distances_to_rows")
+        out.append(torch.stack([w.mean() for w in ws]))
+    return torch.stack(out, 1)
+
+
+def swd(images_a, images_b, P=128, repeats=4, dirs_per_repeat=128, seed=0, value_range=(-1, 1), levels=None, dir_chunk=0, unequal="raise"):
     """SWDResult(levels, mean): the sliced Wasserstein distance x 1e3 of two image sets of one size and count, per pyramid level (finest
-    first) and averaged.  Both sets use the same positions and the same ``repeats * dirs_per_repeat`` directions, drawn from ``seed``."""
+    first) and averaged.  Both sets use the same positions and the same ``repeats * dirs_per_repeat`` directions, drawn from ``seed``.
+    ``unequal="exact"``: (Na, 3, H, W) against (Nb, 3, H, W); the positions are one ``draw`` over max(Na, Nb) images, image i of either set
+    gets those of image i, and every direction's distance is the exact W1 of the two unequal samples."""
+    _check_unequal(unequal, "swd")
     _require_cuda(images_a, images_b)
-    if images_a.dim() != 4 or tuple(images_a.shape) != tuple(images_b.shape):
-        raise ValueError(f"swd: two sets of one shape (N, 3, H, W), got {tuple(images_a.shape)} / {tuple(images_b.shape)}; unequal counts "
-                         "are not supported")
-    n, _, h, w = images_a.shape
+    if unequal == "raise":
+        if images_a.dim() != 4 or tuple(images_a.shape) != tuple(images_b.shape):
+            raise ValueError(f"swd: two sets of one shape (N, 3, H, W), got {tuple(images_a.shape)} / {tuple(images_b.shape)}; unequal "
+                             "counts are not supported")
+    elif images_a.dim() != 4 or images_b.dim() != 4 or tuple(images_a.shape[1:]) != tuple(images_b.shape[1:]):
+        raise ValueError(f"swd: two sets (Na, 3, H, W) and (Nb, 3, H, W) of one image size, got {tuple(images_a.shape)} / "
+                         f"{tuple(images_b.shape)}")
+    na, nb = images_a.shape[0], images_b.shape[0]
+    _, _, h, w = images_a.shape
     if levels is None:
         levels = default_levels(h, w)
     shapes = check_levels(h, w, levels)
-    pos, dirs = draw(seed, levels, shapes, n, int(P), int(repeats) * int(dirs_per_repeat))
-    da = descriptors(images_a, pos, value_range, levels)
-    db = descriptors(images_b, pos, value_range, levels)
-    return report(distances(da, db, dirs, dir_chunk).tolist())
+    pos, dirs = draw(seed, levels, shapes, max(na, nb), int(P), int(repeats) * int(dirs_per_repeat))
+    da = descriptors(images_a, pos[:, :na], value_range, levels)
+    db = descriptors(images_b, pos[:, :nb], value_range, levels)
+    return report(distances(da, db, dirs, dir_chunk, unequal).tolist())
+
+
+# ----------------------------------------------------------------------------------------------
+# descriptor banks: sets of any two counts
+# ----------------------------------------------------------------------------------------------
+class DescriptorBank:
+    """The raw per-level descriptors of a stream of image batches, kept on the device (75 KB per image and level at P = 128): one side of
+    ``compare``, or the ``reference=`` of ``wu.evaluate.SlicedWasserstein``.  ``add(images)``: (B, 3, H, W) float32, bfloat16 or uint8
+    CUDA, one image size for the whole stream; image i of the stream gets the positions ``draw`` gives image i, so any split into batches
+    equals one call, bit for bit, and two banks of one ``signature()`` have used the same positions for their common images."""
+
+    def __init__(self, P=128, repeats=4, dirs_per_repeat=128, seed=0, value_range=(-1, 1), levels=None):
+        self.P, self.ndirs, self.seed = int(P), int(repeats) * int(dirs_per_repeat), seed
+        self.value_range, self.levels = value_range, levels
+        self.count, self.shape, self.mapping, self.parts = 0, None, None, []
+
+    @torch.no_grad()
+    def add(self, images):
+        _require_cuda(images)
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f"DescriptorBank.add: images must be (B, 3, H, W), got {tuple(images.shape)}")
+        b, _, h, w = images.shape
+        mapping = tuple(range_mapping(self.value_range)[:2])
+        if self.shape is None:
+            self.shape, self.mapping = (h, w), mapping
+            if self.levels is None:
+                self.levels = default_levels(h, w)
+        elif self.shape != (h, w) or self.mapping != mapping:
+            raise ValueError(f"DescriptorBank.add: {h} x {w} mapped {mapping} after {self.shape[0]} x {self.shape[1]} mapped {self.mapping}")
+        shapes = check_levels(h, w, self.levels)
+        pos, _ = draw(self.seed, self.levels, shapes, b, self.P, self.ndirs, first=self.count)
+        self.parts.append(descriptors(images, pos, self.value_range, self.levels))
+        self.count += b
+        return self
+
+    def signature(self):
+        """What two banks must share to be compared: P, seed, ndirs, levels, the image size and the (scale, shift) of the value range."""
+        if not self.parts:
+            raise RuntimeError("DescriptorBank: no batch has been added yet")
+        return {"P": self.P, "seed": self.seed, "ndirs": self.ndirs, "levels": self.levels, "image size": self.shape,
+                "value-range mapping": self.mapping}
+
+    def descriptors(self):
+        """[(count * P, 147) float32 CUDA per level]; the batches are joined once and kept joined."""
+        self.signature()
+        if len(self.parts) > 1:
+            self.parts = [[torch.cat([part[l] for part in self.parts]) for l in range(self.levels)]]
+        return self.parts[0]
+
+    def directions(self):
+        """The (ndirs, 147) float32 directions of ``draw`` for this bank's seed."""
+        return draw(self.seed, self.levels, check_levels(*self.shape, self.levels), 1, 1, self.ndirs)[1]
+
+    @classmethod
+    def from_dir(cls, dir, size=None, filter=None, gpu_decode=False, device="cuda:0", batch_size=64, **kwargs):
+        """The bank of every .jpg / .png file of ``dir`` in sorted order, read through ``wu.files.read_images`` (``size``, ``filter``,
+        ``gpu_decode`` as there); ``kwargs`` go to the constructor.  The value range is the reader's."""
+        from .files import image_files, read_images
+        files = image_files(dir)
+        if not files:
+            raise RuntimeError(f"no .jpg / .png images in {dir}")
+        bank = cls(**kwargs)
+        for x, value_range in read_images(files, size, gpu_decode, device, batch_size, filter=filter):
+            bank.value_range = value_range
+            bank.add(x)
+        return bank
+
+
+def check_comparable(sig_a, sig_b, what):
+    """ValueError naming the entries in which two ``DescriptorBank.signature()`` dictionaries differ."""
+    differ = [f"{k} {sig_a[k]} / {sig_b[k]}" for k in sig_a if sig_a[k] != sig_b[k]]
+    if differ:
+        raise ValueError(f"{what}: the two sides must share P, seed, ndirs, levels, image size and value-range mapping; they differ in "
+                         + ", ".join(differ))
+
+
+def compare(bank_a, bank_b, dir_chunk=0):
+    """SWDResult of two ``DescriptorBank``s of any two image counts: per level and direction the exact W1 of the two samples (equal counts:
+    the bits of ``swd`` on the same images).  ValueError unless the banks share ``signature()``."""
+    check_comparable(bank_a.signature(), bank_b.signature(), "compare")
+    return report(distances_to_rows(bank_a.descriptors(), [bank_b.descriptors()], bank_a.directions(), dir_chunk)[0].tolist())
 
 
 # ----------------------------------------------------------------------------------------------
 # command line
 # ----------------------------------------------------------------------------------------------
 def swd_of_dirs(dir_a, dir_b, size=None, P=128, repeats=4, dirs_per_repeat=128, seed=0, gpu_decode=False, device="cuda:0", log=print,
-                filter=None):
+                filter=None, unequal="subset"):
     """SWDResult of the .jpg / .png files of two directories, and the number of images used per set.  Images are resized (through
     ``wu.input_pipeline``) only with ``size``; otherwise mixed sizes are an error.  Directories of unequal count: a random subset of the
     larger one, drawn from ``seed``, and a line through ``log`` that says so.  ``filter`` (box, bilinear, bicubic, lanczos; with ``size``):
-    resize with that Pillow filter in 8-bit mode through ``wu.resample`` instead."""
+    resize with that Pillow filter in 8-bit mode through ``wu.resample`` instead.  ``unequal="exact"``: every image of both directories
+    (``compare`` of two ``DescriptorBank.from_dir``); the second value is then the pair (images of dir_a, images of dir_b)."""
     from .evaluate import SlicedWasserstein
     from .files import image_files, read_images
+    if unequal not in ("subset", "exact"):
+        raise ValueError(f"swd_of_dirs: unequal must be \"subset\" or \"exact\", got {unequal!r}")
     fa, fb = image_files(dir_a), image_files(dir_b)
     if not fa or not fb:
         raise RuntimeError(f"no .jpg / .png images in {dir_a if not fa else dir_b}")
+    if unequal == "exact":
+        banks = [DescriptorBank.from_dir(d, size, filter, gpu_decode, device, P=P, repeats=repeats, dirs_per_repeat=dirs_per_repeat, seed=seed)
+                 for d in (dir_a, dir_b)]
+        return compare(*banks), (banks[0].count, banks[1].count)
     n = min(len(fa), len(fb))
     if len(fa) != len(fb):
         big = fa if len(fa) > n else fb
@@ -308,14 +451,18 @@ def main(argv=None):
     ap.add_argument("--filter", default=None, choices=["box", "bilinear", "bicubic", "lanczos"],
                     help="with --size: resize with this Pillow filter (Image.resize, 8-bit) through wu.resample; absent: the training "
                          "pipeline's bilinear resize, as before")
+    ap.add_argument("--unequal", default="subset", choices=["subset", "exact"],
+                    help="directories of unequal count: subset (default) compares a seeded random subset of the larger one; exact uses "
+                         "every image of both and takes the exact W1 of the unequal samples per direction")
     args = ap.parse_args(argv)
     if args.filter is not None and not args.size:
         ap.error("--filter chooses how --size resizes: give --size")
-    r, n = swd_of_dirs(args.dir_a, args.dir_b, args.size, args.patches, args.repeats, args.dirs, args.seed, args.gpu_decode, filter=args.filter)
+    r, n = swd_of_dirs(args.dir_a, args.dir_b, args.size, args.patches, args.repeats, args.dirs, args.seed, args.gpu_decode, filter=args.filter,
+                       unequal=args.unequal)
     for l, v in enumerate(r.levels):
         print(f"SWD x 1e3, level {l}: {v:.4f}")
     print(f"SWD x 1e3, mean: {r.mean:.4f}")
-    print(f"images per set: {n}")
+    print(f"images: {n[0]} against {n[1]}" if args.unequal == "exact" else f"images per set: {n}")
     return 0
 
 
