@@ -982,6 +982,41 @@ int wu_swd_sort_columns(double* keys, int m, int ncols, void* workspace, void* s
 int wu_swd_distance(const double* a, const double* b, int m, int ndirs, double* w, void* stream);
 int wu_swd_distance_unequal(const double* a, int m1, const double* b, int m2, int ndirs, double* w, void* stream);
 
+/* ---- Radial power spectrum of image luma (wu/spectrum.py; Durall et al. 2020, Dzanic et al. 2020) ---------------------------------------
+ * A 2-D DFT of any side up to 1024 as two matrix products against twiddle tables on the fp64 matrix cores, then the azimuthal average over
+ * integer radial bins.  Stream-ordered on caller-owned buffers, no allocation, no synchronisation, no floating-point atomics: the same
+ * inputs give the same bits, and an image's profile does not depend on which images share its call.  tests/_spectrum_ref.py restates the
+ * arithmetic.  Every product and sum outside the matrix cores is rounded on its own.
+ *   wu_spectrum_luma      x (N, C, H, W) with ELEMENT strides, C 1 or 3, dtype WU_F32, WU_BF16 or WU_SSIM_U8 -> planes (N, H, W) fp64:
+ *                         s = (double(v) * scale + shift) / L; y = (0.299 s_R + 0.587 s_G) + 0.114 s_B (C = 1: y = s); with the window
+ *                         tables wh (H doubles) and ww (W doubles), both DEVICE arrays or both NULL, y = (y * wh[i]) * ww[j].
+ *   wu_spectrum_profiles_planes
+ *                         planes (N, H, W) fp64; cw / sw (W doubles) and ch / sh (H doubles) are DEVICE tables of cos / sin(2 pi k / n).
+ *                         Wh = W / 2 + 1.  Row stage: Tr[i][v] = sum_j y[i][j] cw[(v j) mod W], Ti[i][v] = -sum_j y[i][j] sw[(v j) mod W];
+ *                         column stage: Xr[u][v] = sum_i (ch[(u i) mod H] Tr[i][v] + sh[(u i) mod H] Ti[i][v]),
+ *                         Xi[u][v] = sum_i (ch[(u i) mod H] Ti[i][v] - sh[(u i) mod H] Tr[i][v]); P = Xr Xr + Xi Xi.  Entry (u, v) has
+ *                         mirror weight 2 for 0 < 2 v < W and 1 otherwise, and radial bin k = isqrt(q M^2) / (H W) in int64 with
+ *                         fu = u <= H / 2 ? u : u - H, q = fu^2 W^2 + v^2 H^2, M = min(H, W).  prof (N, K):
+ *                         prof[n][k] = (sum of weight P over the bin) / (sum of weights) / (H W)^2, the sum taken per 64 x 64 tile (entries
+ *                         in row-major order) and then over tiles ascending.  K must be wu_spectrum_bins(H, W).  spectrum_sum, when not
+ *                         NULL, is (H, Wh) fp64 and receives spectrum_sum[u][v] += P[n][u][v] for n ascending (the caller zeroes it):
+ *                         the column stage is then launched once per image and adds P in its epilogue, so no 2-D spectrum other than
+ *                         that sum reaches memory.  workspace: wu_spectrum_workspace_bytes(N, H, W), the (N, H, 2 Wh) fp64
+ *                         intermediate, the per-tile partial sums and the per-tile bin order.
+ *   wu_spectrum_profiles  the same from the strided source: luma and window are applied while the row stage stages its tile, no fp64
+ *                         plane exists in memory; bit for bit wu_spectrum_luma followed by wu_spectrum_profiles_planes.
+ * 1 <= N <= 65535 (the column stage puts the image in grid.y), 1 <= H, W <= 1024.  wu_spectrum_workspace_bytes and wu_spectrum_bins return 0 for anything out of range. */
+int wu_spectrum_bins(int H, int W);
+size_t wu_spectrum_workspace_bytes(int N, int H, int W);
+int wu_spectrum_luma(const void* x, long long xs_n, long long xs_c, long long xs_h, long long xs_w, int dtype, int N, int C, int H, int W,
+                     double scale, double shift, double L, const double* wh, const double* ww, double* planes, void* stream);
+int wu_spectrum_profiles_planes(const double* planes, int N, int H, int W, const double* cw, const double* sw, const double* ch,
+                                const double* sh, int K, void* workspace, double* prof, double* spectrum_sum, void* stream);
+int wu_spectrum_profiles(const void* x, long long xs_n, long long xs_c, long long xs_h, long long xs_w, int dtype, int N, int C, int H,
+                         int W, double scale, double shift, double L, const double* wh, const double* ww, const double* cw,
+                         const double* sw, const double* ch, const double* sh, int K, void* workspace, double* prof,
+                         double* spectrum_sum, void* stream);
+
 /* ---- Colour-transfer baselines (wu/colour.py): histogram matching and sliced optimal transport of pixel colours --------------------------
  * A "virtual image" g = r B + b is input image b on its way to target r; its state is (3, n) fp64 in [0, 1] units, n = H W.  `first` is the
  * g of the first state of a call, so that any run of virtual images can be in flight.  All arithmetic in fp64, every operation rounded on

@@ -193,6 +193,11 @@ SIGNATURES = {
     "wu_swd_sort_columns": (I, [P, I, I, P, P]),
     "wu_swd_distance": (I, [P, P, I, I, P, P]),
     "wu_swd_distance_unequal": (I, [P, I, P, I, I, P, P]),
+    "wu_spectrum_bins": (I, [I, I]),
+    "wu_spectrum_workspace_bytes": (SZ, [I, I, I]),
+    "wu_spectrum_luma": (I, [P] + [ctypes.c_longlong] * 4 + [I, I, I, I, I, c_double, c_double, c_double, P, P, P, P]),
+    "wu_spectrum_profiles_planes": (I, [P, I, I, I, P, P, P, P, I, P, P, P, P]),
+    "wu_spectrum_profiles": (I, [P] + [ctypes.c_longlong] * 4 + [I, I, I, I, I, c_double, c_double, c_double] + [P] * 6 + [I, P, P, P, P]),
     "wu_colour_ot_workspace_bytes": (SZ, [I, I, I, I]),
     "wu_colour_ot_load": (I, [P] + [ctypes.c_longlong] * 4 + [I, I, I, I, c_double, c_double, c_double, ctypes.c_longlong, I, P, P]),
     "wu_colour_ot_palette_keys": (I, [P, I, I, P, P, P, P]),

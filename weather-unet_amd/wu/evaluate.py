@@ -13,6 +13,9 @@
                                                                through ``swd=``
 * ``PerceptualDistance``     (no counterpart in the reference) LPIPS (``wu.lpips``) between every image and its transferred versions, per row,
                                                                and the pairwise-diversity score among the rows; fed through ``lpips=``
+* ``SpectralDiscrepancy``    (no counterpart in the reference) the radial power spectrum (``wu.spectrum``) of the photographs against their
+                                                               transferred versions: log-spectral distance, band differences and the
+                                                               largest single-bin difference, per row; fed through ``spectrum=``
 
 No pandas, plotting or path conventions: callers feed batches (e.g. from ``wu.data.JpegBatchLoader``).  Every ``update`` accumulates on the
 device and never synchronises with the host; ``confusion`` / ``report`` / ``result`` read the accumulators back.  The generator and the
@@ -248,6 +251,59 @@ class SlicedWasserstein:
         return out if self.rows is not None else out[0]
 
 
+class SpectralDiscrepancy:
+    """At which frequencies do the outputs depart from the photographs?  ``wu.spectrum`` accumulated over a data set.  ``update(real, fake)``:
+    real (B, C, H, W), fake (B, C, H, W) or (R, B, C, H, W) as ``sweep`` returns it (R and the image size fixed across calls); each side's
+    radial profiles go into a ``wu.spectrum.SpectrumBank`` (two sums per bin, fp64 on the device, no host synchronisation).  ``compute()``:
+    a ``wu.spectrum.SpectrumResult`` (side a = the photographs, side b = the outputs), or a list of R of them when ``fake`` came with rows.
+    ``reference``: a ``SpectrumBank``, or a list of R of them, one per row, used in place of ``real`` (``update`` then ignores ``real``);
+    it must share this accumulator's image size, window and value-range mapping (ValueError in ``compute``)."""
+
+    def __init__(self, value_range=(-1, 1), window="none", reference=None):
+        from . import spectrum
+        if window not in spectrum.WINDOWS:
+            raise ValueError(f"SpectralDiscrepancy: window must be one of {spectrum.WINDOWS}, got {window!r}")
+        self.value_range, self.window = value_range, window
+        self.reference = list(reference) if isinstance(reference, (list, tuple)) else reference
+        self.rows, self.real, self.fake = None, None, None
+
+    @torch.no_grad()
+    def update(self, real, fake):
+        from . import spectrum
+        if not (torch.is_tensor(real) and torch.is_tensor(fake) and real.is_cuda and fake.is_cuda):
+            raise RuntimeError("wu.evaluate.SpectralDiscrepancy: CUDA tensors only -- no CPU fallback")
+        if real.dim() != 4 or fake.dim() not in (4, 5) or tuple(fake.shape[-4:]) != tuple(real.shape):
+            raise ValueError(f"SpectralDiscrepancy.update: real (B, C, H, W) and fake (B, C, H, W) or (R, B, C, H, W), got "
+                             f"{tuple(real.shape)} / {tuple(fake.shape)}")
+        rows = fake.shape[0] if fake.dim() == 5 else None
+        if self.fake is None:
+            self.rows = rows
+            self.real = spectrum.SpectrumBank(self.value_range, self.window)
+            self.fake = [spectrum.SpectrumBank(self.value_range, self.window) for _ in range(rows if rows is not None else 1)]
+        elif self.rows != rows:
+            raise ValueError(f"SpectralDiscrepancy.update: rows {rows} after rows {self.rows}")
+        if self.reference is None:
+            self.real.add(real)
+        for bank, f in zip(self.fake, fake if rows is not None else fake[None]):
+            bank.add(f)
+
+    def compute(self):
+        from . import spectrum
+        if self.fake is None:
+            raise RuntimeError("no batch has been added yet")
+        nrows = len(self.fake)
+        if self.reference is None:
+            banks = [self.real] * nrows
+        else:
+            banks = self.reference if isinstance(self.reference, list) else [self.reference] * nrows
+            if len(banks) != nrows:
+                raise ValueError(f"SpectralDiscrepancy: {len(banks)} reference banks for {nrows} rows")
+            for bank in banks:
+                spectrum.check_comparable(self.fake[0].signature(), bank.signature(), "SpectralDiscrepancy(reference=)")
+        out = [spectrum.compare(a, b) for a, b in zip(banks, self.fake)]
+        return out if self.rows is not None else out[0]
+
+
 class ClassTransferEval(_Confusion):
     """eval_class_transfer.py:106-136.  ``update(batch)`` transfers every image of the batch to every class (``transfer.sweep`` over the
     identity rows: the encoder runs once per batch), runs ``classifier`` over the nc * B outputs in passes of at most ``max_images`` images
@@ -257,12 +313,14 @@ class ClassTransferEval(_Confusion):
     ``classification_report`` of it.  With the generator's dropout active the masks are those of ``sweep`` (the repeated-batch forward).
     ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per class.
     ``swd``: a ``SlicedWasserstein`` that receives them too (``update(batch, fakes)``), one result per class.
-    ``lpips``: a ``PerceptualDistance`` that receives them too (``add(batch, fakes)``), one row per class."""
+    ``lpips``: a ``PerceptualDistance`` that receives them too (``add(batch, fakes)``), one row per class.
+    ``spectrum``: a ``SpectralDiscrepancy`` that receives them too (``update(batch, fakes)``), one result per class."""
 
-    def __init__(self, transfer, classifier, num_classes, max_images=SWEEP_MAX_IMAGES, names=None, content=None, swd=None, lpips=None):
+    def __init__(self, transfer, classifier, num_classes, max_images=SWEEP_MAX_IMAGES, names=None, content=None, swd=None, lpips=None,
+                 spectrum=None):
         super().__init__(num_classes, names)
         self.transfer, self.classifier, self.max_images, self.content, self.swd = transfer, classifier, int(max_images), content, swd
-        self.lpips = lpips
+        self.lpips, self.spectrum = lpips, spectrum
 
     @torch.no_grad()
     def update(self, batch):
@@ -276,6 +334,8 @@ class ClassTransferEval(_Confusion):
             self.swd.update(batch, fakes)
         if self.lpips is not None:
             self.lpips.add(batch, fakes)
+        if self.spectrum is not None:
+            self.spectrum.update(batch, fakes)
 
 
 class EstimatorTransferEval(_Rows):
@@ -284,12 +344,13 @@ class EstimatorTransferEval(_Rows):
     ``pred - row`` (:54-57); ``result()``: fp64 ``mean`` and population ``std`` over all appended rows (:129-130) and their ``count``.
     ``content``: a ``ContentPreservation`` that also receives every (batch, sweep output), one row per reference row.
     ``swd``: a ``SlicedWasserstein`` that receives them too (``update(batch, fakes)``), one result per reference row.
-    ``lpips``: a ``PerceptualDistance`` that receives them too (``add(batch, fakes)``), one row per reference row."""
+    ``lpips``: a ``PerceptualDistance`` that receives them too (``add(batch, fakes)``), one row per reference row.
+    ``spectrum``: a ``SpectralDiscrepancy`` that receives them too (``update(batch, fakes)``), one result per reference row."""
 
-    def __init__(self, transfer, estimator, max_images=SWEEP_MAX_IMAGES, content=None, swd=None, lpips=None):
+    def __init__(self, transfer, estimator, max_images=SWEEP_MAX_IMAGES, content=None, swd=None, lpips=None, spectrum=None):
         super().__init__()
         self.transfer, self.estimator, self.max_images, self.content, self.swd = transfer, estimator, int(max_images), content, swd
-        self.lpips = lpips
+        self.lpips, self.spectrum = lpips, spectrum
 
     @torch.no_grad()
     def update(self, batch, ref_signals):
@@ -304,6 +365,8 @@ class EstimatorTransferEval(_Rows):
             self.swd.update(batch, fakes)
         if self.lpips is not None:
             self.lpips.add(batch, fakes)
+        if self.spectrum is not None:
+            self.spectrum.update(batch, fakes)
 
 
 class ClassifierEval(_Confusion):
